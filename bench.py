@@ -6,8 +6,15 @@ One "step" = one pass of prl_hip_binarize_batch_device over the whole resident b
 rank owns its own batch (independent pages => no data-path collective; weak scaling).
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the
+statistics of the timed path's last call.  `--full` adds every other leg (roofline: per-kernel timing,
+rocprofv3 traffic and clock passes, the measured ceilings; parity against the CPU oracle and OpenCV;
+the CPU baseline; worst case; end to end); each leg's own option still switches it on or off
+explicitly.  `--dump-outputs DIR` writes the masks of the last timed step (see dump_outputs).
 
 Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).  `roofline.achieved` is the
 algorithmic byte count of one launch (1 B read + 1 B written per output pixel) over the average
@@ -31,6 +38,10 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
+# the legs beside the headline: their value under --full; a plain run leaves every one at 0 unless it is given explicitly
+FULL_DEFAULTS = {"cpu_seconds": 15.0, "check_pages": 8, "traffic": 1, "ceilings": 1, "worst_case": 1, "end_to_end": 1}
+DUMP_BYTES = 64_000_000   # --dump-outputs writes at most this much in all
+
 
 def parse():
     ap = argparse.ArgumentParser()
@@ -45,29 +56,38 @@ def parse():
     ap.add_argument("--k", type=float, default=0.34)
     ap.add_argument("--morph", type=int, default=0)
     ap.add_argument("--mode", default="auto", choices=["auto", "literal"])
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline leg (0 = skip)")
-    ap.add_argument("--check-pages", type=int, default=8,
-                    help="pages verified against the oracle after timing (spread over the batch: first, last, evenly between)")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg beside the headline (the options below default to their value in brackets; a plain run: 0)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the masks of the last timed step to DIR/*.npy (float32; a seeded sample when the batch is large)")
+    ap.add_argument("--cpu-seconds", type=float, default=None, help="budget of the CPU baseline leg (0 = skip) [15]")
+    ap.add_argument("--check-pages", type=int, default=None,
+                    help="pages verified against the oracle after timing (spread over the batch: first, last, evenly between) [8]")
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong", "both"],
                     help="weak: --pages per GPU; strong: --pages in total, split over the ranks by dist.page_range; both (only "
-                         "with --gpus > 1): the weak line is THE line, the strong-scaling measurement rides in it as `strong`")
-    ap.add_argument("--traffic", type=int, default=1,
+                         "with --gpus > 1, where --full makes it the default): the weak line is THE line, the strong-scaling "
+                         "measurement rides in it as `strong`")
+    ap.add_argument("--traffic", type=int, default=None,
                     help="1: measure roofline.traffic in this run - two child passes of this benchmark under rocprofv3 --pmc "
-                         "(FETCH_SIZE, WRITE_SIZE), started before this process touches the GPU (N=1 only); 0: traffic = null")
-    ap.add_argument("--ceilings", type=int, default=1, help="1: time the hand-written read / write / copy kernels on this batch")
-    ap.add_argument("--worst-case", type=int, default=1,
+                         "(FETCH_SIZE, WRITE_SIZE), started before this process touches the GPU (N=1 only); 0: traffic = null [1]")
+    ap.add_argument("--ceilings", type=int, default=None, help="1: time the hand-written read / write / copy kernels on this batch [1]")
+    ap.add_argument("--worst-case", type=int, default=None,
                     help="1 (N=1 only): after the timed region, the same pages through the literal pipeline and a batch of adversarial "
-                         "pages (every second pixel inside the float32 decision band) through auto mode -> `worst_case`")
+                         "pages (every second pixel inside the float32 decision band) through auto mode -> `worst_case` [1]")
     ap.add_argument("--adversarial-pages", type=int, default=0, help="pages of the adversarial batch (0: as many as the headline's batch)")
-    ap.add_argument("--end-to-end", type=int, default=1,
+    ap.add_argument("--end-to-end", type=int, default=None,
                     help="1 (N=1 only): the batch as a host page list in pinned memory through prl_hip_binarize_batch_host "
-                         "(H2D + kernels + D2H) -> `end_to_end` (SURVEY.md 8d's second number; never `value`)")
+                         "(H2D + kernels + D2H) -> `end_to_end` (SURVEY.md 8d's second number; never `value`) [1]")
     ap.add_argument("--digest", type=int, default=0,
                     help="1: the line carries `page_digests`, the CRC-32 of every page's mask in page-list order (all ranks) - "
                          "lets a test compare an N-rank run with the single-process run of the same page list")
     ap.add_argument("--lib", default=None, help="A/B tooling: load this build of libprlib_hip.so instead of the in-tree one")
     ap.add_argument("--hooks", type=int, default=0, help="A/B tooling: 1 = load libprlib_hip_testhooks.so (reads the PRL_HIP_* tuning knobs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    for key, full_value in FULL_DEFAULTS.items():
+        if getattr(args, key) is None:
+            setattr(args, key, full_value if args.full else type(full_value)(0))
+    return args
 
 
 def spawn_ranks(args) -> int:
@@ -318,6 +338,34 @@ def end_to_end_leg(prlib_amd, dev, pages, params, g, W, H):
         pin_out.close()
 
 
+def dump_outputs(out_dir, out, n_pages, out_h, out_w):
+    """--dump-outputs: what the timed path handed its caller in its last step - the masks (0 / 255) of this rank's pages, pitch
+    padding dropped - as float32 .npy files of at most DUMP_BYTES in all, so that two builds can be compared output for output
+    (the pages are seeded: the same arguments give the same inputs).
+      mask.npy             the whole N x out_h x out_w batch when it fits half the budget; otherwise the pixels at a fixed
+                           sample of positions (numpy default_rng(0), sorted, unique; flat index over N x out_h x out_w)
+      mask_row_counts.npy  the foreground (255) pixels of every mask row, N x out_h (the first pages that fit the other half)"""
+    import numpy as np
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    masks = out[:n_pages, :, :out_w]
+    half = DUMP_BYTES // 2
+    total = n_pages * out_h * out_w
+    if total * 4 <= half:
+        mask = masks.cpu().numpy().astype(np.float32)
+    else:
+        idx = np.unique(np.random.default_rng(0).integers(0, total, half // 4, dtype=np.int64))
+        p, rem = np.divmod(idx, out_h * out_w)
+        r, c = np.divmod(rem, out_w)
+        pos = torch.from_numpy(p * out.stride(0) + r * out.stride(1) + c).to(out.device)   # (out: one contiguous pitched buffer)
+        mask = out.reshape(-1).index_select(0, pos).cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "mask.npy"), mask)
+    n_rows = max(1, min(n_pages, half // (out_h * 4)))
+    counts = masks[:n_rows].ne(0).sum(dim=2, dtype=torch.int32).cpu().numpy().astype(np.float32)
+    np.save(os.path.join(out_dir, "mask_row_counts.npy"), counts)
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -326,8 +374,8 @@ def main():
         sys.exit(spawn_ranks(args))
     if args.scaling == "both" and args.gpus == 1:
         args.scaling = "weak"
-    elif args.scaling == "weak" and args.gpus > 1:
-        args.scaling = "both"   # N > 1: the weak-scaling line carries the strong-scaling measurement as well (`strong`)
+    elif args.scaling == "weak" and args.gpus > 1 and args.full:
+        args.scaling = "both"   # N > 1, --full: the weak-scaling line carries the strong-scaling measurement as well (`strong`)
     traffic, traffic_note = None, "not measured (--traffic 0 or N > 1)"
     clock = {"shader_clock_ghz": None, "gui_active_cycles_per_launch": None, "clock_note": "not measured (--traffic 0 or N > 1)"}
     under_profiler = any("rocprof" in os.environ.get(k, "").lower() for k in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES", "HSA_TOOLS_LIB"))
@@ -411,23 +459,28 @@ def main():
         step()
     barrier()
     elapsed = pdist.max_over_ranks(time.perf_counter() - t0, device=dev)
+    stats = prlib_amd.last_stats()
+    if args.dump_outputs and rank == 0:   # (before any later leg writes into `out`)
+        dump_outputs(args.dump_outputs, out, n_mine, g.out_h, g.out_w)
 
     # dominant-kernel duration: HIP events recorded by the library around k_fused on the launch stream
     # ... and around everything the call enqueues (prl_hip_last_call_ms): the other sweeps of Wolf-Jolion, refinement, fix-up,
-    # the morphology pass - what one prl::binarize*() call costs on the device
-    _capi.check(L.prl_hip_set_profiling(1))
-    kms, cms = [], []
-    for _ in range(max(3, min(args.steps, 10))):
-        step()
-        ms = C.c_float(0)
-        _capi.check(L.prl_hip_last_kernel_ms(C.byref(ms)))
-        kms.append(ms.value)
-        _capi.check(L.prl_hip_last_call_ms(C.byref(ms)))
-        cms.append(ms.value)
-    _capi.check(L.prl_hip_set_profiling(0))
-    kernel_ms = sum(kms) / len(kms)
-    call_ms = sum(cms) / len(cms)
-    stats = prlib_amd.last_stats()
+    # the morphology pass - what one prl::binarize*() call costs on the device.  Runs steps of its own: --full (or a roofline
+    # leg asked for by name) only
+    kernel_ms = call_ms = None
+    if args.full or args.traffic or args.ceilings:
+        _capi.check(L.prl_hip_set_profiling(1))
+        kms, cms = [], []
+        for _ in range(max(3, min(args.steps, 10))):
+            step()
+            ms = C.c_float(0)
+            _capi.check(L.prl_hip_last_kernel_ms(C.byref(ms)))
+            kms.append(ms.value)
+            _capi.check(L.prl_hip_last_call_ms(C.byref(ms)))
+            cms.append(ms.value)
+        _capi.check(L.prl_hip_set_profiling(0))
+        kernel_ms = sum(kms) / len(kms)
+        call_ms = sum(cms) / len(cms)
 
     # measured ceilings of this box beside the 8 TB/s spec peak: hand-written dwordx4 kernels (16 B per lane,
     # non-temporal, grid-stride) on THIS batch - read-only (the page batch), write-only (the mask batch), copy (pages -> a scratch
@@ -454,19 +507,48 @@ def main():
     px_per_step_total = total_pages * g.out_w * g.out_h
     bytes_per_px = 3 if method == prlib_amd.WOLFJOLION else 2
     alg_bytes = n_mine * (H * W * (bytes_per_px - 1) + g.out_w * g.out_h)   # rank 0's launch
-    dominant_gbs = alg_bytes / (kernel_ms * 1e-3) / 1e9
-    call_gbs = alg_bytes / (call_ms * 1e-3) / 1e9
-    # calls with more than one heavy kernel (Wolf-Jolion's three sweeps, a morphology pass) are priced on the WHOLE call
-    multi_kernel = method == prlib_amd.WOLFJOLION or args.morph != 0 or args.mode != "auto"
-    achieved_gbs = call_gbs if multi_kernel else dominant_gbs
+    roofline = None
+    if kernel_ms is not None:
+        dominant_gbs = alg_bytes / (kernel_ms * 1e-3) / 1e9
+        call_gbs = alg_bytes / (call_ms * 1e-3) / 1e9
+        # calls with more than one heavy kernel (Wolf-Jolion's three sweeps, a morphology pass) are priced on the WHOLE call
+        multi_kernel = method == prlib_amd.WOLFJOLION or args.morph != 0 or args.mode != "auto"
+        achieved_gbs = call_gbs if multi_kernel else dominant_gbs
+        roofline = {
+            "bound": "hbm",
+            "achieved": round(achieved_gbs, 1),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
+            "frac_basis": "whole call (several heavy kernels: algorithmic bytes / call_ms)" if multi_kernel
+                          else "dominant kernel (algorithmic bytes / kernel_ms; the call's other kernels are in frac_whole_call)",
+            "frac_dominant_kernel": round(dominant_gbs / HBM_PEAK_GBS, 4),
+            "frac_whole_call": round(call_gbs / HBM_PEAK_GBS, 4),
+            "traffic": traffic,
+            "traffic_note": traffic_note,
+            # which box this was: the kernel's own clock and what a wavefront-row cost in SIMD cycles (a build's speed is the
+            # second number, a box's the first)
+            "shader_clock_ghz": clock["shader_clock_ghz"],
+            "simd_cycles_per_wavefront_row": simd_cycles_per_row(clock, args, W, g, n_mine),
+            "clock_note": clock["clock_note"],
+            # (windows of 33..129 columns run their threshold sweep in k_fused_q)
+            "kernel": ("k_fused_q" if 32 <= args.window - 1 <= 128 else "k_fused") if args.mode == "auto" else "literal chain",
+            "kernel_ms": round(kernel_ms, 4),
+            "call_ms": round(call_ms, 4),
+            "algorithmic_bytes_per_launch": alg_bytes,
+            "measured_read_gbs": ceil["measured_read_gbs"],
+            "measured_write_gbs": ceil["measured_write_gbs"],
+            "measured_copy_gbs": ceil["measured_copy_gbs"],
+            "frac_of_measured_copy": round(achieved_gbs / ceil["measured_copy_gbs"], 4) if ceil["measured_copy_gbs"] else None,
+        }
 
     # parity spot check (outside the timed region): first pages against the CPU oracle
     mismatches = None
     checked = []
     cpu = None
     vs_opencv = None
-    vs_opencv_why = None
-    if rank == 0:
+    vs_opencv_why = None if args.full else "not run: --full only"
+    if rank == 0 and (args.full or args.check_pages > 0 or args.cpu_seconds > 0):
         from oracle import capi as oc
 
         po = oc.make_params(method, args.window, args.k, args.morph)
@@ -480,7 +562,7 @@ def main():
             got = out.index_select(0, sel)[:, :, : g.out_w].cpu().numpy()
             mismatches = int((want != got).sum())
             checked = idx
-        if world == 1:
+        if world == 1 and args.full:
             try:   # the oracle against real OpenCV where this box has it (None: not installed, parity unpinned)
                 from oracle import opencv_check
 
@@ -554,33 +636,7 @@ def main():
                 "parallelism": f"pages sharded over {world} GPU(s), no collectives",
                 "dist_backend": pdist.backend_name(),   # only the barrier and the max-over-ranks of the time go through it
             },
-            "roofline": {
-                "bound": "hbm",
-                "achieved": round(achieved_gbs, 1),
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": round(achieved_gbs / HBM_PEAK_GBS, 4),
-                "frac_basis": "whole call (several heavy kernels: algorithmic bytes / call_ms)" if multi_kernel
-                              else "dominant kernel (algorithmic bytes / kernel_ms; the call's other kernels are in frac_whole_call)",
-                "frac_dominant_kernel": round(dominant_gbs / HBM_PEAK_GBS, 4),
-                "frac_whole_call": round(call_gbs / HBM_PEAK_GBS, 4),
-                "traffic": traffic,
-                "traffic_note": traffic_note,
-                # which box this was: the kernel's own clock and what a wavefront-row cost in SIMD cycles (a build's speed is the
-                # second number, a box's the first)
-                "shader_clock_ghz": clock["shader_clock_ghz"],
-                "simd_cycles_per_wavefront_row": simd_cycles_per_row(clock, args, W, g, n_mine),
-                "clock_note": clock["clock_note"],
-                # (windows of 33..129 columns run their threshold sweep in k_fused_q)
-                "kernel": ("k_fused_q" if 32 <= args.window - 1 <= 128 else "k_fused") if args.mode == "auto" else "literal chain",
-                "kernel_ms": round(kernel_ms, 4),
-                "call_ms": round(call_ms, 4),
-                "algorithmic_bytes_per_launch": alg_bytes,
-                "measured_read_gbs": ceil["measured_read_gbs"],
-                "measured_write_gbs": ceil["measured_write_gbs"],
-                "measured_copy_gbs": ceil["measured_copy_gbs"],
-                "frac_of_measured_copy": round(achieved_gbs / ceil["measured_copy_gbs"], 4) if ceil["measured_copy_gbs"] else None,
-            },
+            "roofline": roofline,   # (null in a plain run: per-kernel timing takes steps of its own, --full)
             "cpu_baseline": cpu,
             "parity": {"checked_pages": checked, "mismatching_pixels": mismatches,
                        "refined_pixels": int(stats.refined_pixels), "exact_pixels": int(stats.exact_pixels),

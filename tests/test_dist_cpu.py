@@ -108,14 +108,14 @@ def test_bench_launcher_path_two_ranks_dryrun():
     env = dict(os.environ, PRL_BENCH_DRYRUN="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--pages", "5"]
+           "--pages", "5", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
     assert d == {"dryrun": True, "n_gpus": 2, "pages_total": 10, "max_rank_plus_1": 2.0, "first_block": [0, 5], "blocks": [[0, 5], [5, 10]],
-                 "scaling": "weak", "strong_ride_along": True}   # N > 1: the weak line also carries the strong-scaling measurement
+                 "scaling": "weak", "strong_ride_along": True}   # N > 1, --full: the weak line also carries the strong-scaling measurement
 
 
 def _run_bench(argv, extra_env=None):

@@ -17,8 +17,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "2", "--warmup", "1", "--size", "1024", "--traffic", "0", "--ceilings", "0", "--cpu-seconds", "0",
-          "--worst-case", "0", "--end-to-end", "0", "--digest", "1"]
+COMMON = ["--full", "--steps", "2", "--warmup", "1", "--size", "1024", "--traffic", "0", "--ceilings", "0", "--cpu-seconds", "0",
+          "--worst-case", "0", "--end-to-end", "0", "--digest", "1"]   # (--full: the parity check against the oracle)
 
 
 def _free_port():

@@ -5,7 +5,7 @@ for rep in 1 2 3 4; do
  for cfg in "niblack 101 0.01 2 2480 3508" "sauvola 101 0.34 0 2480 3508" "sauvola 51 0.34 0 4096 4096"; do
   set -- $cfg
   for q in 0 1 2; do
-    PRL_HIP_FUSED_QINT=$q python3 bench.py --hooks 1 --pages 256 --size $5 --height $6 --method $1 --window $2 --k $3 --morph $4 --steps 6 --warmup 2 --worst-case 0 --end-to-end 0 --traffic 0 --cpu-seconds 0 --check-pages 2 2>/dev/null | tail -1 | python3 -c "
+    PRL_HIP_FUSED_QINT=$q python3 bench.py --full --hooks 1 --pages 256 --size $5 --height $6 --method $1 --window $2 --k $3 --morph $4 --steps 6 --warmup 2 --worst-case 0 --end-to-end 0 --traffic 0 --cpu-seconds 0 --check-pages 2 2>/dev/null | tail -1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('qint=$q', '$1 $2 morph $4 $5x$6', d['ms_per_step'], d['roofline']['kernel_ms'], d['roofline'].get('kernel'), d['parity']['mismatching_pixels'])"
   done
  done

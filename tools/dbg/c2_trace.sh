@@ -2,7 +2,7 @@
 # kernels of one single-page call (config 2: one 4096^2 page, Sauvola w=15): names, durations, gaps
 cd "$(dirname "$0")/../.."
 OUT=$PWD/gpurun_out/c2_trace; rm -rf $OUT; mkdir -p $OUT; export TMPDIR=/tmp
-timeout 200 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/t -- python3 bench.py --pages 1 --size 4096 --window 15 --steps 20 --warmup 3 --cpu-seconds 0 --check-pages 0 > $OUT/log.txt 2>&1
+timeout 200 rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d $OUT/t -- python3 bench.py --full --pages 1 --size 4096 --window 15 --steps 20 --warmup 3 --cpu-seconds 0 --check-pages 0 > $OUT/log.txt 2>&1
 python3 - "$OUT" <<'PY'
 import csv, glob, os, sys
 rows = []

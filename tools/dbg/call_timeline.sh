@@ -6,7 +6,7 @@ cd "$(dirname "$0")/../.."
 export TMPDIR=/tmp
 M=${1:-feng}; W=${2:-21}; K=${3:-0.0}; MO=${4:-2}; SZ=${5:-4096}; H=${6:-4096}; P=${7:-256}
 OUT=$PWD/gpurun_out/call_timeline; rm -rf $OUT; mkdir -p $OUT
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python3 bench.py --pages $P --size $SZ --height $H --method $M --window $W --k $K --morph $MO --steps 3 --warmup 1 --cpu-seconds 0 --check-pages 0 --traffic 0 --ceilings 0 --worst-case 0 --end-to-end 0 > $OUT/log.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python3 bench.py --full --pages $P --size $SZ --height $H --method $M --window $W --k $K --morph $MO --steps 3 --warmup 1 --cpu-seconds 0 --check-pages 0 --traffic 0 --ceilings 0 --worst-case 0 --end-to-end 0 > $OUT/log.txt 2>&1
 f=$(find $OUT/t -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys

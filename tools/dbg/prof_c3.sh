@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../.."
 export TMPDIR=/tmp
 for cfg in "--pages 256 --size 2480 --height 3508 --method niblack --window 101 --k 0.01 --morph 2" "--pages 256 --size 4096 --morph 2" "--pages 256 --size 2480 --height 3508 --method niblack --window 31 --k 0.01 --morph 2"; do
   OUT=$PWD/gpurun_out/prof_c3; rm -rf $OUT; mkdir -p $OUT
-  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -- python3 bench.py $cfg --steps 5 --warmup 1 --cpu-seconds 0 --check-pages 0 > $OUT/log.txt 2>&1
+  timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/t -- python3 bench.py --full $cfg --steps 5 --warmup 1 --cpu-seconds 0 --check-pages 0 > $OUT/log.txt 2>&1
   f=$(find $OUT/t -name "*kernel_stats.csv" | head -1)
   echo "== $cfg"
   python3 - "$f" <<'PY'

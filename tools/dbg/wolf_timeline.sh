@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/../.."
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/wolf_timeline; rm -rf $OUT; mkdir -p $OUT
-timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python3 bench.py --pages ${PAGES:-256} --size 2480 --height 3508 --method wolfjolion --window ${WIN:-101} --k 0.01 --morph ${MORPH:-2} --steps 3 --warmup 1 --cpu-seconds 0 --check-pages 0 --traffic 0 --ceilings 0 --worst-case 0 --end-to-end 0 > $OUT/log.txt 2>&1
+timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/t -- python3 bench.py --full --pages ${PAGES:-256} --size 2480 --height 3508 --method wolfjolion --window ${WIN:-101} --k 0.01 --morph ${MORPH:-2} --steps 3 --warmup 1 --cpu-seconds 0 --check-pages 0 --traffic 0 --ceilings 0 --worst-case 0 --end-to-end 0 > $OUT/log.txt 2>&1
 f=$(find $OUT/t -name "*kernel_trace.csv" | head -1)
 python3 - "$f" <<'PY'
 import csv, sys
