@@ -362,6 +362,26 @@ int prl_hip_bgnorm_batch_device(int n_pages, int channels, const uint8_t* d_src,
 int prl_hip_bgnorm_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
                         size_t dst_step);
 
+/* ---- salt-and-pepper denoising (prl::denoiseSaltPepper) ----------------------------------------------------------- */
+
+/*
+ * prl::denoiseSaltPepper(in, out, kernelSize, times) (src/denoise/denoiseSaltPepper.h:40, .cpp:29-36) = `times` passes of
+ * cv::medianBlur(out, out, kernelSize) over a copy of the input: out(y, x, c) is the value at rank (k*k - 1) / 2 of the
+ * k x k window around (y, x) in channel c, BORDER_REPLICATE, each pass reading the previous pass's result.  Exact for every
+ * odd ksize up to 65535 (a window larger than the page included).  8-bit pages of 1..4 interleaved channels; 2 channels only
+ * with ksize <= 5 (cv::medianBlur's k > 5 path takes 1, 3, 4).  ksize == 1 or times == 0 copies.  Sizes: width, height
+ * <= 32768.  d_src == d_dst with the same strides (in place) is allowed; any other overlap returns PRL_ERR_BAD_ARG, and d_src
+ * is otherwise never written.  Passes alternate between d_dst and the device's cached scratch (R x H bytes per page,
+ * R = width * channels, when times >= 2 or in place).  Enqueues on `stream`, no synchronisation.
+ * PRL_ERR_EMPTY: width or height <= 0; PRL_ERR_BAD_WINDOW: ksize < 1 or even; PRL_ERR_BAD_CHANNELS: channels outside 1..4, or
+ * 2 with ksize >= 7; PRL_ERR_BAD_ARG: null pointer, negative n_pages, step < row bytes, size above the limits.
+ */
+int prl_hip_median_batch_device(int n_pages, int channels, int ksize, size_t times, const uint8_t* d_src, size_t src_page_stride,
+                                size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                void* stream);
+int prl_hip_median_host(int channels, int ksize, size_t times, const uint8_t* src, size_t src_step, int width, int height,
+                        uint8_t* dst, size_t dst_step);
+
 /* ---- local-variance binarizers ------------------------------------------------------------- */
 
 /*

@@ -52,6 +52,7 @@ EXPORTED_SYMBOLS = [
     "prl_hip_rotate_host", "prl_hip_deskew_host", "prl_hip_find_angle_batch_device", "prl_hip_find_angle_host", "prl_hip_last_deskew_stats", "prl_hip_reset_deskew_stats", "prl_hip_set_literal_page_budget", "prl_hip_get_literal_page_budget", "prl_hip_chain_max_out_size", "prl_hip_chain_pages_device",
     "prl_hip_binarize_batch_host", "prl_hip_page_range", "prl_hip_binarize_lv_batch_device", "prl_hip_binarize_lv_host",
     "prl_hip_chain_batch_host", "prl_hip_alloc_host", "prl_hip_free_host", "prl_hip_host_register", "prl_hip_host_unregister",
+    "prl_hip_median_batch_device", "prl_hip_median_host",
 ]
 
 
@@ -171,6 +172,8 @@ def lib() -> C.CDLL:
         L.prl_hip_page_range.argtypes = [i, i, i, P(C.c_int), P(C.c_int)]
         L.prl_hip_binarize_lv_batch_device.argtypes = [i, i, C.c_double, i, C.c_double, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_binarize_lv_host.argtypes = [i, C.c_double, i, C.c_double, vp, sz, i, i, vp, sz]
+        L.prl_hip_median_batch_device.argtypes = [i, i, i, sz, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_median_host.argtypes = [i, i, sz, vp, sz, i, i, vp, sz]
         _lib = L
     return _lib
 

@@ -9,6 +9,7 @@
 //   src/binarizations/binarizeNICK.h:43-47                 prl::binarizeNICK
 //   src/binarizations/binarizeFeng.h:46-53                 prl::binarizeFeng
 //   src/denoise/denoiseNLM.h:32                            prl::denoise
+//   src/denoise/denoiseSaltPepper.h:40                     prl::denoiseSaltPepper
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -54,6 +55,14 @@ CV_EXPORTS void binarizeFeng(cv::Mat& inputImage, cv::Mat& outputImage, int wind
                   int morphIterationCount = 2);
 
 CV_EXPORTS void denoise(const cv::Mat& inputImage, cv::Mat& outputImage, double strength = 5.5);
+
+// src/denoise/denoiseSaltPepper.h:40 - out = in.clone(), then `times` passes of cv::medianBlur(out, out, kernelSize) (.cpp:29-36):
+// the exact median of every kernelSize x kernelSize window, BORDER_REPLICATE, channels independent.  times == 0: a clone of any
+// Mat.  Otherwise cv::Exception: StsAssert for an empty input or an even / non-positive kernelSize, and for 2 channels with
+// kernelSize >= 7 ([upstream] medianBlur's k > 5 path); StsUnsupportedFormat for a depth other than CV_8U or more than 4
+// channels (OpenCV also takes 16U / 16S / 32F at k <= 5: not here).  The output is a new continuous Mat; the input's pixels
+// are never written (out may be in, or a view of it).
+CV_EXPORTS void denoiseSaltPepper(const cv::Mat& in, cv::Mat& out, int kernelSize, size_t times);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

@@ -151,6 +151,38 @@ void prl::denoise(const cv::Mat& inputImage, cv::Mat& outputImage, double streng
     outputImage = result;
 }
 
+// denoiseSaltPepper.cpp:29-36: out = in.clone(); for (times) cv::medianBlur(out, out, kernelSize).  The checks below are
+// cv::medianBlur's; `out` holds the clone before any of them throws, as in the reference.
+void prl::denoiseSaltPepper(const cv::Mat& in, cv::Mat& out, int kernelSize, size_t times)
+{
+    if (times == 0) {
+        out = in.clone();
+        return;
+    }
+    const char* fail = nullptr;
+    int code = cv::Error::StsAssert;
+    if (in.empty()) fail = "!_src0.empty()";                        // [upstream] OpenCV >= 4
+    else if (kernelSize % 2 != 1) fail = "(ksize % 2 == 1) && (_src0.dims() <= 2 )";
+    else if (in.depth() != CV_8U || in.channels() > 4) {
+        code = cv::Error::StsUnsupportedFormat;                       // documented deviation: 8-bit only
+        fail = "prl::denoiseSaltPepper: 8-bit images of 1..4 channels only";
+    } else if (in.channels() == 2 && kernelSize >= 7) {
+        fail = "cn == 1 || cn == 3 || cn == 4";                       // [upstream] medianBlur's k > 5 path
+    }
+    if (fail) {
+        out = in.clone();
+        PRL_FAIL_CV(code, fail);
+    }
+    cv::Mat result(in.rows, in.cols, in.type());
+    const int st = prl_hip_median_host(in.channels(), kernelSize, times, in.data, in.step, in.cols, in.rows, result.data,
+                                       result.step);
+    if (st != PRL_OK) {
+        out = in.clone();
+        raise(st);
+    }
+    out = result;
+}
+
 namespace {
 void lv_impl(int with_filters, cv::Mat& in, cv::Mat& out, double coeff, int minVar, double gamma, const char* empty_msg)
 {

@@ -135,6 +135,7 @@ struct EnvKnobs {
     int host_copy_threads = 0;          // PRL_HIP_HOST_COPY_THREADS  threads of the pool that copies pageable pages in / out of pinned memory (0: half of the cores, at most 32)
     unsigned segmax_cap = 1u << 20;     // PRL_HIP_SEGMAX_CAP   wavefronts per Wolf-Jolion call (tests shrink it)
     int literal_mode = 0;         // PRL_HIP_MODE=literal
+    bool median_generic = false;  // PRL_HIP_MEDIAN_GENERIC=1  the histogram kernel for every window (median.hip), k = 3 and 5 included
 };
 const EnvKnobs& env_knobs();
 
