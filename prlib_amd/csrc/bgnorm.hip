@@ -360,18 +360,18 @@ int prl_hip_bgnorm_batch_device(int n_pages, int channels, const uint8_t* d_src,
     const int chunk = std::min(n_pages, 16384);
     st = ensure_scratch(ctx, bgnorm_work_bytes(chunk, channels, width, height));
     if (st != PRL_OK) return st;
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(hs, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    st = device_acquire(ctx, hs);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, hs};
     for (int first = 0; first < n_pages; first += chunk) {
         PageSet s{};
         s.base = d_src + (size_t)first * src_page_stride; s.page_stride = src_page_stride; s.step = src_step;
         PageSetOut d{};
         d.base = d_dst + (size_t)first * dst_page_stride; d.page_stride = dst_page_stride; d.step = dst_step;
         st = bgnorm_run(std::min(chunk, n_pages - first), channels, s, width, height, d, ctx->scratch, hs);
-        if (st != PRL_OK) break;
+        if (st != PRL_OK) return st;
     }
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, hs));
-    return st;
+    return PRL_OK;
 }
 
 int prl_hip_bgnorm_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
@@ -380,26 +380,12 @@ int prl_hip_bgnorm_host(int channels, const uint8_t* src, size_t src_step, int w
     if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
     const int och = channels == 1 ? 1 : 3;
     if (!dst || src_step < (size_t)width * channels || dst_step < (size_t)width * och) return PRL_ERR_BAD_ARG;
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
     const size_t in_row = (size_t)width * channels, out_row = (size_t)width * och;
-    const size_t in_bytes = (in_row * (size_t)height + 255) / 256 * 256, out_bytes = out_row * (size_t)height;
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);
-    st = ensure_stage(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
-    uint8_t* d_out = d_in + in_bytes;
-    hipStream_t stream = nullptr;
-    DrainOnExit drain_guard{stream};   // (direct DMA from the caller's pinned page: see prl_internal.h)
-    st = stage_upload(ctx, 0, src, src_step, in_row, height, d_in, stream);
-    if (st != PRL_OK) return st;
-    st = prl_hip_bgnorm_batch_device(1, channels, d_in, in_bytes, in_row, width, height, d_out, out_bytes, out_row, stream);
-    if (st != PRL_OK) return st;
-    return stage_download(ctx, in_bytes, d_out, out_row, height, dst, dst_step, stream);
+    return stage_host_page(src, src_step, in_row, height, dst, dst_step, out_row, height,
+                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
+                               return prl_hip_bgnorm_batch_device(1, channels, d_in, in_bytes, in_row, width, height, d_out, out_bytes,
+                                                                  out_row, s);
+                           });
 }
 
 }  // extern "C"

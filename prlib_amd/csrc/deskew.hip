@@ -947,8 +947,6 @@ int launch_warp(int channels, const PageSet& s, const PageSetOut& d, int width, 
     return PRL_OK;
 }
 
-size_t r256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 // Totals of the Hough searches since the last prl_hip_reset_deskew_stats (process-wide: the chain searches on a helper thread).
@@ -1318,9 +1316,10 @@ int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, 
 {
     if (plan.warp.size() != sizeof(WarpPage) * (size_t)cnt) return PRL_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(hs, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
-    int st = ensure_small(ctx, plan.warp.size());
+    int st = device_acquire(ctx, hs);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, hs};
+    st = ensure_small(ctx, plan.warp.size());
     if (st != PRL_OK) return st;
     ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
     PRL_HIP_CHECK(hipMemcpyAsync(ctx->small, plan.warp.data(), plan.warp.size(), hipMemcpyHostToDevice, hs));
@@ -1329,10 +1328,7 @@ int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, 
     s.base = src; s.page_stride = src_page_stride; s.step = src_step;
     PageSetOut d{};
     d.base = dst; d.page_stride = dst_page_stride; d.step = dst_step;
-    st = launch_warp(channels, s, d, width, height, cnt, plan.max_ow, plan.max_oh, static_cast<const WarpPage*>(ctx->small), hs);
-    if (st != PRL_OK) return st;
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, hs));
-    return PRL_OK;
+    return launch_warp(channels, s, d, width, height, cnt, plan.max_ow, plan.max_oh, static_cast<const WarpPage*>(ctx->small), hs);
 }
 
 int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
@@ -1421,8 +1417,9 @@ int prl_hip_rotate_batch_device(int n_pages, int channels, const double* angles,
     st = ensure_small(ctx, sizeof(WarpPage) * (size_t)chunk);
     if (st != PRL_OK) return st;
     ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(hs, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    st = device_acquire(ctx, hs);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, hs};
     std::vector<WarpPage> wp((size_t)chunk);
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
@@ -1442,7 +1439,6 @@ int prl_hip_rotate_batch_device(int n_pages, int channels, const double* angles,
         st = launch_warp(channels, s, d, width, height, cnt, max_ow, max_oh, static_cast<const WarpPage*>(ctx->small), hs);
         if (st != PRL_OK) return st;
     }
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, hs));
     return PRL_OK;
 }
 

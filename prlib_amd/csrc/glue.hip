@@ -241,8 +241,6 @@ int prl_hip_invert_batch_device(int n_pages, const uint8_t* d_src, size_t src_pa
 // equal size (all pages of a skewed batch come out max(W,H) square: one run).
 namespace {
 
-size_t r256(size_t v) { return (v + 255) / 256 * 256; }
-
 struct ChainLayout {   // per page of a uniform run, each part rounded up to 256 B
     size_t denoised, normalised, gray, mask, total;
     int ch_after;      // channels of the page the gray conversion sees

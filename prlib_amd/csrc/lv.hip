@@ -362,13 +362,14 @@ int prl_hip_binarize_lv_batch_device(int n_pages, int with_filters, double coeff
     DeviceCtx* ctx = device_ctx(dev);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t plane = ((size_t)width * height + 255) / 256 * 256;
+    const size_t plane = r256((size_t)width * height);
     const int chunk = std::min(n_pages, 16384);
-    const size_t stats_bytes = ((size_t)chunk * (sizeof(LvStats) + sizeof(LvConsts)) + 255) / 256 * 256;
+    const size_t stats_bytes = r256((size_t)chunk * (sizeof(LvStats) + sizeof(LvConsts)));
     st = ensure_scratch(ctx, stats_bytes + (with_filters ? 2 * plane * (size_t)chunk : 0));
     if (st != PRL_OK) return st;
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(hs, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    st = device_acquire(ctx, hs);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, hs};
     LvStats* d_stats = static_cast<LvStats*>(ctx->scratch);
     LvConsts* d_consts = reinterpret_cast<LvConsts*>(d_stats + chunk);
     uint8_t* G = static_cast<uint8_t*>(ctx->scratch) + stats_bytes;
@@ -392,7 +393,6 @@ int prl_hip_binarize_lv_batch_device(int n_pages, int with_filters, double coeff
         if (with_filters) hipLaunchKernelGGL(k_lv_final, grid, dim3(256), 0, hs, p, G, NR, plane, d);
         PRL_HIP_CHECK(hipGetLastError());
     }
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, hs));
     return PRL_OK;
 }
 
@@ -401,27 +401,12 @@ int prl_hip_binarize_lv_host(int with_filters, double coeff, int min_result_vari
 {
     if (width <= 0 || height <= 0 || !src) return PRL_ERR_EMPTY;
     if (!dst || src_step < (size_t)width * 3 || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
     const size_t in_row = (size_t)width * 3, out_row = (size_t)width;
-    const size_t in_bytes = (in_row * (size_t)height + 255) / 256 * 256, out_bytes = out_row * (size_t)height;
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);
-    st = ensure_stage(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
-    uint8_t* d_out = d_in + in_bytes;
-    hipStream_t stream = nullptr;
-    DrainOnExit drain_guard{stream};   // (direct DMA from the caller's pinned page: see prl_internal.h)
-    st = stage_upload(ctx, 0, src, src_step, in_row, height, d_in, stream);
-    if (st != PRL_OK) return st;
-    st = prl_hip_binarize_lv_batch_device(1, with_filters, coeff, min_result_variance, gamma, d_in, in_bytes, in_row, width, height,
-                                          d_out, out_bytes, out_row, stream);
-    if (st != PRL_OK) return st;
-    return stage_download(ctx, in_bytes, d_out, out_row, height, dst, dst_step, stream);
+    return stage_host_page(src, src_step, in_row, height, dst, dst_step, out_row, height,
+                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
+                               return prl_hip_binarize_lv_batch_device(1, with_filters, coeff, min_result_variance, gamma, d_in, in_bytes,
+                                                                       in_row, width, height, d_out, out_bytes, out_row, s);
+                           });
 }
 
 }  // extern "C"

@@ -426,8 +426,9 @@ int prl_hip_median_batch_device(int n_pages, int channels, int ksize, size_t tim
         st = ensure_scratch(ctx, page_bytes * (size_t)chunk);
         if (st != PRL_OK) return st;
     }
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(hs, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    st = device_acquire(ctx, hs);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, hs};
     for (int first = 0; first < n_pages; first += chunk) {
         PageSet s{};
         s.base = d_src + (size_t)first * src_page_stride; s.page_stride = src_page_stride; s.step = src_step;
@@ -435,10 +436,9 @@ int prl_hip_median_batch_device(int n_pages, int channels, int ksize, size_t tim
         d.base = d_dst + (size_t)first * dst_page_stride; d.page_stride = dst_page_stride; d.step = dst_step;
         st = median_run(g, work ? times : 0, s, d, std::min(chunk, n_pages - first), in_place,
                         need_tmp ? static_cast<uint8_t*>(ctx->scratch) : nullptr, hs);
-        if (st != PRL_OK) break;
+        if (st != PRL_OK) return st;
     }
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, hs));
-    return st;
+    return PRL_OK;
 }
 
 int prl_hip_median_host(int channels, int ksize, size_t times, const uint8_t* src, size_t src_step, int width, int height,
@@ -450,25 +450,11 @@ int prl_hip_median_host(int channels, int ksize, size_t times, const uint8_t* sr
     const size_t row = (size_t)width * channels;
     if (!src || !dst || src_step < row || dst_step < row) return PRL_ERR_BAD_ARG;
     if (width > kMedMaxSide || height > kMedMaxSide || ksize > kMedMaxK) return PRL_ERR_BAD_ARG;
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    const size_t in_bytes = (row * (size_t)height + 255) / 256 * 256, out_bytes = row * (size_t)height;
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);
-    st = ensure_stage(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
-    uint8_t* d_out = d_in + in_bytes;
-    hipStream_t stream = nullptr;
-    DrainOnExit drain_guard{stream};   // (direct DMA from the caller's pinned page: see prl_internal.h)
-    st = stage_upload(ctx, 0, src, src_step, row, height, d_in, stream);
-    if (st != PRL_OK) return st;
-    st = prl_hip_median_batch_device(1, channels, ksize, times, d_in, in_bytes, row, width, height, d_out, out_bytes, row, stream);
-    if (st != PRL_OK) return st;
-    return stage_download(ctx, in_bytes, d_out, row, height, dst, dst_step, stream);
+    return stage_host_page(src, src_step, row, height, dst, dst_step, row, height,
+                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
+                               return prl_hip_median_batch_device(1, channels, ksize, times, d_in, in_bytes, row, width, height, d_out,
+                                                                  out_bytes, row, s);
+                           });
 }
 
 }  // extern "C"

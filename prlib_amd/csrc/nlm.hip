@@ -831,10 +831,11 @@ static int lab_tables(DeviceCtx* ctx, hipStream_t s, LabTables* lt)
 static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
                              int height, uint8_t* planes, hipStream_t s)
 {
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(s, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    int st = device_acquire(ctx, s);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, s};
     LabTables lt{};
-    int st = lab_tables(ctx, s, &lt);
+    st = lab_tables(ctx, s, &lt);
     if (st != PRL_OK) return st;
     const size_t px = (size_t)width * height;
     uint8_t* L = planes;
@@ -844,14 +845,14 @@ static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_
     const dim3 grid((width + 255) / 256, height, cnt);
     hipLaunchKernelGGL(k_lbgr2lab, grid, dim3(256), 0, s, ps, channels, width, height, lt, L, AB, px);
     PRL_HIP_CHECK(hipGetLastError());
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, s));
     return PRL_OK;
 }
 
 static int nlm_locked(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int width, int height, hipStream_t s)
 {
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(s, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    int st = device_acquire(ctx, s);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, s};
     const size_t px = (size_t)width * height;
     uint8_t* L = planes;
     uint8_t* AB = L + px * (size_t)cnt;
@@ -863,21 +864,19 @@ static int nlm_locked(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, 
     PageSetOut dl{}, dab{};
     dl.base = L2; dl.page_stride = px; dl.step = (size_t)width;
     dab.base = AB2; dab.page_stride = 2 * px; dab.step = 2 * (size_t)width;
-    int st = nlm_planes_locked(ctx, 0, cnt, 1, strength, sl, width, height, dl, s);
+    st = nlm_planes_locked(ctx, 0, cnt, 1, strength, sl, width, height, dl, s);
     if (st != PRL_OK) return st;
-    st = nlm_planes_locked(ctx, 1, cnt, 2, 3.0f, sab, width, height, dab, s);  // hForColorComponents = 3
-    if (st != PRL_OK) return st;
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, s));
-    return PRL_OK;
+    return nlm_planes_locked(ctx, 1, cnt, 2, 3.0f, sab, width, height, dab, s);  // hForColorComponents = 3
 }
 
 static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, uint8_t* dst,
                               size_t dst_page_stride, size_t dst_step, hipStream_t s)
 {
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(s, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    int st = device_acquire(ctx, s);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, s};
     LabTables lt{};
-    int st = lab_tables(ctx, s, &lt);
+    st = lab_tables(ctx, s, &lt);
     if (st != PRL_OK) return st;
     const size_t px = (size_t)width * height;
     const uint8_t* L2 = planes + 3 * px * (size_t)cnt;
@@ -887,7 +886,6 @@ static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8
     const dim3 grid((width + 255) / 256, height, cnt);
     hipLaunchKernelGGL(k_lab2lbgr, grid, dim3(256), 0, s, L2, AB2, px, channels, width, height, lt, pd);
     PRL_HIP_CHECK(hipGetLastError());
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, s));
     return PRL_OK;
 }
 
@@ -940,8 +938,9 @@ int prl_hip_nlm_planes_device(int n_pages, int channels, float h, const uint8_t*
     st = ensure_small(ctx, 2 * kLutSlot + 64 * 1024);
     if (st != PRL_OK) return st;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(s, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    st = device_acquire(ctx, s);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, s};
     PageSet ps{};
     ps.base = d_src;
     ps.page_stride = src_page_stride;
@@ -950,10 +949,7 @@ int prl_hip_nlm_planes_device(int n_pages, int channels, float h, const uint8_t*
     pd.base = d_dst;
     pd.page_stride = dst_page_stride;
     pd.step = dst_step;
-    st = nlm_planes_locked(ctx, 0, n_pages, channels, h, ps, width, height, pd, s);
-    if (st != PRL_OK) return st;
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, s));
-    return PRL_OK;
+    return nlm_planes_locked(ctx, 0, n_pages, channels, h, ps, width, height, pd, s);
 }
 
 int prl_hip_denoise_batch_device(int n_pages, int channels, float strength, const uint8_t* d_src,
@@ -995,25 +991,12 @@ int prl_hip_denoise_host(int channels, float strength, const uint8_t* src, size_
     if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
     if (channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
     if (!src || !dst || src_step < (size_t)width * channels || dst_step < (size_t)width * channels) return PRL_ERR_BAD_ARG;
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
     const size_t row = (size_t)width * channels;
-    const size_t bytes = (row * (size_t)height + 255) / 256 * 256;
-    DeviceCtx* ctx = device_ctx(dev);
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);  // cached device + pinned staging (lock order: stage_mu, then mu)
-    st = ensure_stage(ctx, 2 * bytes);
-    if (st != PRL_OK) return st;
-    st = ensure_stage_pinned(ctx, 2 * bytes);
-    if (st != PRL_OK) return st;
-    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
-    uint8_t* d_out = d_in + bytes;
-    DrainOnExit drain_guard{nullptr};   // (direct DMA from the caller's pinned page: see prl_internal.h)
-    st = stage_upload(ctx, 0, src, src_step, row, height, d_in, nullptr);
-    if (st != PRL_OK) return st;
-    st = prl_hip_denoise_batch_device(1, channels, strength, d_in, bytes, row, width, height, d_out, bytes, row, nullptr);
-    if (st != PRL_OK) return st;
-    return stage_download(ctx, bytes, d_out, row, height, dst, dst_step, nullptr);
+    return stage_host_page(src, src_step, row, height, dst, dst_step, row, height,
+                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
+                               return prl_hip_denoise_batch_device(1, channels, strength, d_in, in_bytes, row, width, height, d_out,
+                                                                   out_bytes, row, s);
+                           });
 }
 
 }  // extern "C"

@@ -748,8 +748,6 @@ __global__ void __launch_bounds__(kGrpThreads) k_ppht_group(GrpArgs a)
     }
 }
 
-size_t r256(size_t v) { return (v + 255) / 256 * 256; }
-
 }  // namespace
 
 // Geometry of the group kernel for W x H pages: members per group (0: the page does not qualify), angle tables.

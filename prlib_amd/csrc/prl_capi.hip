@@ -252,75 +252,69 @@ DeviceCtx* device_ctx(int dev)
     return p.get();
 }
 
-int ensure_buffer(void** buf, size_t* have, size_t bytes)
+hipError_t free_buffer(void** buf, size_t* have)
 {
-    if (*have >= bytes) return PRL_OK;
-    if (*buf) {
-        PRL_HIP_CHECK(hipDeviceSynchronize());
-        PRL_HIP_CHECK(hipFree(*buf));
+    const hipError_t e = *buf ? hipFree(*buf) : hipSuccess;
+    if (e == hipSuccess) {
         *buf = nullptr;
         *have = 0;
     }
+    return e;
+}
+
+hipError_t free_host_buffer(void** buf, size_t* have)
+{
+    const hipError_t e = *buf ? hipHostFree(*buf) : hipSuccess;
+    if (e == hipSuccess) {
+        *buf = nullptr;
+        *have = 0;
+    }
+    return e;
+}
+
+int ensure_buffer(void** buf, size_t* have, size_t bytes)
+{
+    if (*have >= bytes) return PRL_OK;
+    if (*buf) PRL_HIP_CHECK(hipDeviceSynchronize());
+    PRL_HIP_CHECK(free_buffer(buf, have));
     PRL_HIP_CHECK(hipMalloc(buf, bytes));
     *have = bytes;
     return PRL_OK;
 }
 
-int ensure_scratch(DeviceCtx* ctx, size_t bytes)
+int ensure_host_buffer(void** buf, size_t* have, size_t bytes)
 {
-    if (ctx->scratch_bytes >= bytes) return PRL_OK;
-    if (ctx->scratch) {
-        PRL_HIP_CHECK(hipDeviceSynchronize());
-        PRL_HIP_CHECK(hipFree(ctx->scratch));
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-    }
-    PRL_HIP_CHECK(hipMalloc(&ctx->scratch, bytes));
-    ctx->scratch_bytes = bytes;
+    if (*have >= bytes) return PRL_OK;
+    if (*buf) PRL_HIP_CHECK(hipDeviceSynchronize());
+    PRL_HIP_CHECK(free_host_buffer(buf, have));
+    PRL_HIP_CHECK(hipHostMalloc(buf, bytes, hipHostMallocDefault));
+    *have = bytes;
     return PRL_OK;
 }
 
-int ensure_mask(DeviceCtx* ctx, size_t bytes)
-{
-    if (ctx->mask_bytes >= bytes) return PRL_OK;
-    if (ctx->mask) {
-        PRL_HIP_CHECK(hipDeviceSynchronize());
-        PRL_HIP_CHECK(hipFree(ctx->mask));
-        ctx->mask = nullptr;
-        ctx->mask_bytes = 0;
-    }
-    PRL_HIP_CHECK(hipMalloc(&ctx->mask, bytes));
-    ctx->mask_bytes = bytes;
-    return PRL_OK;
-}
+int ensure_scratch(DeviceCtx* ctx, size_t bytes) { return ensure_buffer(&ctx->scratch, &ctx->scratch_bytes, bytes); }
 
 int ensure_small(DeviceCtx* ctx, size_t bytes)
 {
     if (ctx->small_bytes >= bytes) return PRL_OK;
-    if (ctx->small) {
-        PRL_HIP_CHECK(hipDeviceSynchronize());
-        PRL_HIP_CHECK(hipFree(ctx->small));
-        ctx->small = nullptr;
-        ctx->small_bytes = 0;
-    }
     ctx->lut_small[0] = ctx->lut_small[1] = nullptr;  // cached NL-means tables lived in the old block
-    bytes = std::max<size_t>(bytes, 1 << 20);
-    PRL_HIP_CHECK(hipMalloc(&ctx->small, bytes));
-    ctx->small_bytes = bytes;
-    return PRL_OK;
+    return ensure_buffer(&ctx->small, &ctx->small_bytes, std::max<size_t>(bytes, 1 << 20));
 }
 
-int ensure_stage(DeviceCtx* ctx, size_t bytes)
+int ensure_pinned(DeviceCtx* ctx, size_t bytes)
 {
-    if (ctx->stage_bytes >= bytes) return PRL_OK;
-    if (ctx->stage) {
-        PRL_HIP_CHECK(hipDeviceSynchronize());
-        PRL_HIP_CHECK(hipFree(ctx->stage));
-        ctx->stage = nullptr;
-        ctx->stage_bytes = 0;
-    }
-    PRL_HIP_CHECK(hipMalloc(&ctx->stage, bytes));
-    ctx->stage_bytes = bytes;
+    if (ctx->pinned_bytes >= bytes) return PRL_OK;
+    return ensure_host_buffer(&ctx->pinned, &ctx->pinned_bytes, std::max<size_t>(bytes, 1 << 16));
+}
+
+int ensure_stage(DeviceCtx* ctx, size_t bytes) { return ensure_buffer(&ctx->stage, &ctx->stage_bytes, bytes); }
+
+int ensure_stage_pinned(DeviceCtx* ctx, size_t bytes) { return ensure_host_buffer(&ctx->stage_pinned, &ctx->stage_pinned_bytes, bytes); }
+
+int device_acquire(DeviceCtx* ctx, hipStream_t stream)
+{
+    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(stream, ctx->last_use, 0));
+    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
     return PRL_OK;
 }
 
@@ -338,20 +332,6 @@ int stage_release(DeviceCtx* ctx, hipStream_t stream)
 {
     if (!ctx->stage_use) PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->stage_use, hipEventDisableTiming));
     PRL_HIP_CHECK(hipEventRecord(ctx->stage_use, stream));
-    return PRL_OK;
-}
-
-int ensure_stage_pinned(DeviceCtx* ctx, size_t bytes)
-{
-    if (ctx->stage_pinned_bytes >= bytes) return PRL_OK;
-    if (ctx->stage_pinned) {
-        PRL_HIP_CHECK(hipDeviceSynchronize());
-        PRL_HIP_CHECK(hipHostFree(ctx->stage_pinned));
-        ctx->stage_pinned = nullptr;
-        ctx->stage_pinned_bytes = 0;
-    }
-    PRL_HIP_CHECK(hipHostMalloc(&ctx->stage_pinned, bytes, hipHostMallocDefault));
-    ctx->stage_pinned_bytes = bytes;
     return PRL_OK;
 }
 
@@ -536,21 +516,6 @@ int stage_download(DeviceCtx* ctx, size_t pin_off, const uint8_t* d_src, size_t 
     return PRL_OK;
 }
 
-int ensure_pinned(DeviceCtx* ctx, size_t bytes)
-{
-    if (ctx->pinned_bytes >= bytes) return PRL_OK;
-    if (ctx->pinned) {
-        PRL_HIP_CHECK(hipDeviceSynchronize());
-        PRL_HIP_CHECK(hipHostFree(ctx->pinned));
-        ctx->pinned = nullptr;
-        ctx->pinned_bytes = 0;
-    }
-    bytes = std::max<size_t>(bytes, 1 << 16);
-    PRL_HIP_CHECK(hipHostMalloc(&ctx->pinned, bytes, hipHostMallocDefault));
-    ctx->pinned_bytes = bytes;
-    return PRL_OK;
-}
-
 namespace {
 
 int exec_mode()
@@ -618,8 +583,6 @@ ThrParams make_thr_params(const prl_binarize_params* p, const prl_binarize_geome
     tp.gamma = p->feng_gamma;
     return tp;
 }
-
-size_t r256(size_t v) { return (v + 255) / 256 * 256; }
 
 struct SlotLayout {
     size_t table_bytes, globals_bytes, total;
@@ -1214,44 +1177,21 @@ int prl_hip_release_workspace(void)
         (void)resolve_all(kv.second.get());
     }
     PRL_HIP_CHECK(hipDeviceSynchronize());
-    for (int i = 0; i < DeviceCtx::kPphtBufs; ++i) {
-        if (ctx->ppht_buf[i]) PRL_HIP_CHECK(hipFree(ctx->ppht_buf[i]));
-        ctx->ppht_buf[i] = nullptr;
-        ctx->ppht_bytes[i] = 0;
-    }
+    for (int i = 0; i < DeviceCtx::kPphtBufs; ++i) PRL_HIP_CHECK(free_buffer(&ctx->ppht_buf[i], &ctx->ppht_bytes[i]));
     ctx->ppht_rnd_n = 0;
-    for (int i = 0; i < 4; ++i) {
-        if (ctx->host_buf[i]) PRL_HIP_CHECK(hipFree(ctx->host_buf[i]));
-        ctx->host_buf[i] = nullptr;
-        ctx->host_buf_bytes[i] = 0;
-    }
+    for (int i = 0; i < 4; ++i) PRL_HIP_CHECK(free_buffer(&ctx->host_buf[i], &ctx->host_buf_bytes[i]));
     host_slots_free(ctx);
-    if (ctx->chain_planes) PRL_HIP_CHECK(hipFree(ctx->chain_planes));
-    ctx->chain_planes = nullptr;
-    ctx->chain_planes_bytes = 0;
+    PRL_HIP_CHECK(free_buffer(&ctx->chain_planes, &ctx->chain_planes_bytes));
     for (auto& kv : ctx->streams) {
         std::lock_guard<std::mutex> wl(kv.second->mu);
         ws_free(kv.second.get());
     }
-    if (ctx->scratch) PRL_HIP_CHECK(hipFree(ctx->scratch));
-    ctx->scratch = nullptr;
-    ctx->scratch_bytes = 0;
-    if (ctx->mask) PRL_HIP_CHECK(hipFree(ctx->mask));
-    ctx->mask = nullptr;
-    ctx->mask_bytes = 0;
-    if (ctx->small) PRL_HIP_CHECK(hipFree(ctx->small));
-    ctx->small = nullptr;
-    ctx->small_bytes = 0;
+    PRL_HIP_CHECK(free_buffer(&ctx->scratch, &ctx->scratch_bytes));
+    PRL_HIP_CHECK(free_buffer(&ctx->small, &ctx->small_bytes));
     ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
-    if (ctx->pinned) PRL_HIP_CHECK(hipHostFree(ctx->pinned));
-    ctx->pinned = nullptr;
-    ctx->pinned_bytes = 0;
-    if (ctx->stage) PRL_HIP_CHECK(hipFree(ctx->stage));
-    ctx->stage = nullptr;
-    ctx->stage_bytes = 0;
-    if (ctx->stage_pinned) PRL_HIP_CHECK(hipHostFree(ctx->stage_pinned));
-    ctx->stage_pinned = nullptr;
-    ctx->stage_pinned_bytes = 0;
+    PRL_HIP_CHECK(free_host_buffer(&ctx->pinned, &ctx->pinned_bytes));
+    PRL_HIP_CHECK(free_buffer(&ctx->stage, &ctx->stage_bytes));
+    PRL_HIP_CHECK(free_host_buffer(&ctx->stage_pinned, &ctx->stage_pinned_bytes));
     return PRL_OK;
 }
 
@@ -1364,30 +1304,14 @@ int prl_hip_binarize_host(const prl_binarize_params* p, const uint8_t* src, size
     if (st != PRL_OK) return st;
     if (!src || !dst || src_step < (size_t)width || dst_step < (size_t)g.out_w) return PRL_ERR_BAD_ARG;
     if (padded_out && padded_step < (size_t)g.padded_w) return PRL_ERR_BAD_ARG;
-    int dev;
-    st = current_device(&dev);
-    if (st != PRL_OK) return st;
-
-    // rows packed tightly on the device (the kernels take any step >= width); 256-byte aligned page starts
+    // rows packed tightly on the device (the kernels take any step >= width)
     const size_t in_pitch = (size_t)width, out_pitch = (size_t)g.out_w;
-    const size_t in_bytes = (in_pitch * (size_t)height + 255) / 256 * 256, out_bytes = out_pitch * (size_t)g.out_h;
-    DeviceCtx* ctx = device_ctx(dev);
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);  // cached device + pinned staging: no allocation per page
-    st = ensure_stage(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
-    uint8_t* d_out = d_in + in_bytes;
-    hipStream_t stream = nullptr;
-    DrainOnExit drain_guard{stream};   // (direct DMA from the caller's pinned page: see prl_internal.h)
-    st = stage_upload(ctx, 0, src, src_step, (size_t)width, height, d_in, stream);
-    if (st != PRL_OK) return st;
-    st = prl_hip_binarize_batch_device(p, 1, d_in, in_bytes, in_pitch, width, height, d_out, out_bytes, out_pitch, stream);
-    if (st != PRL_OK) return st;
-    st = prl_hip_finish(stream);  // (deferred-completion mode: the page is final before it is fetched)
-    if (st != PRL_OK) return st;
-    st = stage_download(ctx, in_bytes, d_out, (size_t)g.out_w, g.out_h, dst, dst_step, stream);
+    st = stage_host_page(src, src_step, in_pitch, height, dst, dst_step, out_pitch, g.out_h,
+                         [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
+                             const int r = prl_hip_binarize_batch_device(p, 1, d_in, in_bytes, in_pitch, width, height, d_out,
+                                                                         out_bytes, out_pitch, s);
+                             return r != PRL_OK ? r : prl_hip_finish(s);  // (deferred-completion mode: the page is final before it is fetched)
+                         });
     if (st != PRL_OK) return st;
     if (padded_out) {
         // cv::copyMakeBorder(in, in, h, h, h, h, BORDER_REPLICATE) side effect on the caller's Mat
@@ -1449,12 +1373,10 @@ int prl_hip_morph_batch_device(int morph_iterations, int n_pages, const uint8_t*
     st = ensure_scratch(ctx, tstep * (size_t)height * (size_t)n_pages);
     if (st != PRL_OK) return st;
     hipStream_t hs = static_cast<hipStream_t>(stream);
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(hs, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
-    st = morph_large_run(morph_iterations, s, n_pages, width, height, d, static_cast<uint8_t*>(ctx->scratch), tstep, hs);
+    st = device_acquire(ctx, hs);
     if (st != PRL_OK) return st;
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, hs));
-    return PRL_OK;
+    DeviceRelease release{ctx, hs};
+    return morph_large_run(morph_iterations, s, n_pages, width, height, d, static_cast<uint8_t*>(ctx->scratch), tstep, hs);
 }
 
 }  // extern "C"

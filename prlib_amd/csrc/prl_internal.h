@@ -31,25 +31,17 @@ void set_error_detail(const std::string& s);
 
 struct StreamWs;  // per-(device, stream) workspace of the binarizers (prl_capi.hip)
 
-// The *_host entries may start a DMA straight from / into the CALLER's pinned pixels (stage_upload / stage_download).  Whatever
-// way such an entry returns - also early, on an error of a later step - nothing may still be reading or writing that memory:
-// the stream is drained at scope exit (a no-op after the success path's own wait).
-struct DrainOnExit {
-    hipStream_t s;
-    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
-};
+inline size_t r256(size_t v) { return (v + 255) / 256 * 256; }   // sizes and offsets of 256-byte aligned blocks
 
 // ---- per-device context: cached scratch memory ------------------------------------------------
 struct DeviceCtx {
     std::mutex streams_mu;  // guards `streams` only (never held across device work: deskew holds `mu` for seconds)
     std::map<hipStream_t, std::unique_ptr<StreamWs>> streams;  // the entries have their own locks
     ~DeviceCtx();
-    std::mutex mu;          // one binarize/denoise call at a time per device (scratch is shared)
+    std::mutex mu;          // one call at a time per device on the shared workspace (scratch, small, pinned)
     int device = -1;
-    void* scratch = nullptr;   // literal pipeline: float64 integral planes
+    void* scratch = nullptr;   // page-sized work planes of the batch entries (bgnorm, LV, thinning, NL-means, median, morph)
     size_t scratch_bytes = 0;
-    void* mask = nullptr;      // thresholded masks waiting for the morphology pass
-    size_t mask_bytes = 0;
     void* small = nullptr;  // counters / work lists / per-page globals
     size_t small_bytes = 0;
     std::mutex stage_mu;    // one *_host call at a time per device (taken before `mu`)
@@ -68,10 +60,10 @@ struct DeviceCtx {
     int cu_count = 0;
     hipEvent_t prof_start = nullptr, prof_stop = nullptr;  // prl_hip_set_profiling
     bool prof_valid = false;
-    hipEvent_t last_use = nullptr;  // recorded after each call; the next call's stream waits on it
+    hipEvent_t last_use = nullptr;  // last use of scratch / small / pinned: device_acquire waits on it, DeviceRelease records it
     hipEvent_t stage_use = nullptr; // same for the staging area (`stage`): recorded by its last user (guarded by stage_mu)
     // The angle search of prl::deskew has its own workspace, lock and stream: in the chain it runs for the next pass
-    // while the other stages of the current one use `scratch` / `mask` / `small` (glue.hip).
+    // while the other stages of the current one use `scratch` / `small` (glue.hip).
     std::mutex ppht_mu;
     // fixed part (masks, lists' layout ...), point / segment lists, gray pages, the group kernel's workspace (ppht_group.hip),
     // accumulators in device memory (k_ppht_mw, for the pages the group kernel did not take), cv::RNG's output
@@ -151,10 +143,23 @@ private:
 
 int current_device(int* dev);             // validates that a gfx950 device is usable
 DeviceCtx* device_ctx(int dev);
+// Grow-only cached buffers, one pair per memory kind: device (hipMalloc) and pinned host (hipHostMalloc).  A buffer that has to
+// grow is freed once the whole device has drained, then allocated anew; free_* leave {nullptr, 0} behind.
+int ensure_buffer(void** buf, size_t* have, size_t bytes);
+int ensure_host_buffer(void** buf, size_t* have, size_t bytes);
+hipError_t free_buffer(void** buf, size_t* have);
+hipError_t free_host_buffer(void** buf, size_t* have);
 int ensure_scratch(DeviceCtx* ctx, size_t bytes);
-int ensure_mask(DeviceCtx* ctx, size_t bytes);
-int ensure_small(DeviceCtx* ctx, size_t bytes);
-int ensure_pinned(DeviceCtx* ctx, size_t bytes);
+int ensure_small(DeviceCtx* ctx, size_t bytes);   // at least 1 MiB
+int ensure_pinned(DeviceCtx* ctx, size_t bytes);  // at least 64 KiB
+// The shared device workspace (scratch, small, pinned) serves every stream of the device: under `mu`, a user makes its stream
+// wait for the previous user's work (device_acquire) before the first write; DeviceRelease records its own work as the new
+// last use on every exit of the scope, error exits included (before `mu` is released: declare it after the lock).
+int device_acquire(DeviceCtx* ctx, hipStream_t stream);
+struct DeviceRelease {
+    DeviceCtx* c; hipStream_t s;
+    ~DeviceRelease() { (void)hipEventRecord(c->last_use, s); }
+};
 int ensure_stage(DeviceCtx* ctx, size_t bytes);  // caller holds stage_mu
 // The staging area is shared by every stream of the device: a user makes its stream wait for the previous user's work
 // (stage_acquire) before the first write and records its own work at the end (stage_release).  Caller holds stage_mu.
@@ -173,6 +178,42 @@ int stage_download(DeviceCtx* ctx, size_t pin_off, const uint8_t* d_src, size_t 
                    size_t dst_step, hipStream_t stream);                  // synchronises `stream`
 int ensure_stage_pinned(DeviceCtx* ctx, size_t bytes);
 bool host_range_pinned(const void* p, size_t bytes);   // pinned host memory: the DMA engines may use it directly
+
+// The *_host entries may start a DMA straight from / into the CALLER's pinned pixels (stage_upload / stage_download).  Whatever
+// way such an entry returns - also early, on an error of a later step - nothing may still be reading or writing that memory:
+// the stream is drained at scope exit (a no-op after the success path's own wait).
+struct DrainOnExit {
+    hipStream_t s;
+    ~DrainOnExit() { (void)hipStreamSynchronize(s); }
+};
+// One host page through a device stage, the path of the single-page *_host entries: under stage_mu the cached staging area
+// holds [in | out] at 256-byte offsets; `src` (in_rows rows of in_row bytes) goes up, then
+//     int run(const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t stream)
+// runs the stage on the null stream, and out_rows rows of out_row bytes come down into `dst`.
+template <typename Run>
+int stage_host_page(const uint8_t* src, size_t src_step, size_t in_row, int in_rows, uint8_t* dst, size_t dst_step,
+                    size_t out_row, int out_rows, Run&& run)
+{
+    int dev;
+    int st = current_device(&dev);
+    if (st != PRL_OK) return st;
+    DeviceCtx* ctx = device_ctx(dev);
+    const size_t in_bytes = r256(in_row * (size_t)in_rows), out_bytes = r256(out_row * (size_t)out_rows);
+    std::lock_guard<std::mutex> slk(ctx->stage_mu);  // cached device + pinned staging: no allocation per page (lock order: stage_mu, then mu)
+    st = ensure_stage(ctx, in_bytes + out_bytes);
+    if (st != PRL_OK) return st;
+    st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
+    if (st != PRL_OK) return st;
+    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
+    uint8_t* d_out = d_in + in_bytes;
+    const hipStream_t stream = nullptr;
+    DrainOnExit drain_guard{stream};
+    st = stage_upload(ctx, 0, src, src_step, in_row, in_rows, d_in, stream);
+    if (st != PRL_OK) return st;
+    st = run(d_in, in_bytes, d_out, out_bytes, stream);
+    if (st != PRL_OK) return st;
+    return stage_download(ctx, in_bytes, d_out, out_row, out_rows, dst, dst_step, stream);
+}
 
 // ---- page addressing: contiguous batch or table of page pointers ---------------------------------
 struct PageSet {
@@ -327,8 +368,7 @@ int ppht_group_run(DeviceCtx* ctx, PphtGroupIn& in, hipStream_t stream);
 // glue.hip: pages per pass of the chain and its workspace bytes per page (host_batch.hip sizes device chunks in whole passes)
 int chain_pass_layout(const prl_chain_params* cp, int n_pages, int channels, int width, int height, int* pass_pages,
                       size_t* per_page_out, size_t* desk_page_out);
-int ensure_buffer(void** buf, size_t* have, size_t bytes);
-void host_slots_free(DeviceCtx* ctx);  // host_batch.hip: the pinned bounce slots of prl_hip_chain_batch_host (caller holds host_mu)  // grow-only device buffer (synchronises the device when it grows)
+void host_slots_free(DeviceCtx* ctx);  // host_batch.hip: the pinned bounce slots of prl_hip_chain_batch_host (caller holds host_mu)
 
 // ---- morphology (morph.hip) ------------------------------------------------------------------
 int morph_run(int iterations, const PageSet& src, int n_pages, int width, int height,

@@ -312,7 +312,7 @@ int thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_
     const size_t plane_words = (size_t)wpr * height;
     if (plane_words >= 0x7fffff00ull) return PRL_ERR_BAD_ARG;  // kernels index a page's words with 32 bits
     const size_t bits_bytes = plane_words * sizeof(unsigned) * (size_t)n_pages;
-    const size_t flags_bytes = ((size_t)n_pages * sizeof(unsigned) + 255) / 256 * 256;
+    const size_t flags_bytes = r256((size_t)n_pages * sizeof(unsigned));
     // one launch per pass: strips of 60 words x segments of rows, one wavefront each
     const int n_strips = (wpr + kThinUseful - 1) / kThinUseful;
     int rps = 256;  // measured (16 A4 pages): 32 rows 31 us per pass, 16: 26, 8: 26, 4: 31
@@ -321,11 +321,12 @@ int thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_
     const int n_segs = (height + rps - 1) / rps;
     const unsigned long long tw = (unsigned long long)n_pages * n_strips * n_segs;
     if (tw >= 0xfffffff0ull) return PRL_ERR_BAD_ARG;
-    const size_t act_cap = ((size_t)tw + 255) / 256 * 256;  // one activity byte per tile and pass parity
+    const size_t act_cap = r256((size_t)tw);  // one activity byte per tile and pass parity
     st = ensure_scratch(ctx, 2 * bits_bytes + 2 * flags_bytes + 2 * act_cap);
     if (st != PRL_OK) return st;
-    if (ctx->last_use) PRL_HIP_CHECK(hipStreamWaitEvent(s, ctx->last_use, 0));
-    else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->last_use, hipEventDisableTiming));
+    st = device_acquire(ctx, s);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, s};
     auto* A = static_cast<unsigned*>(ctx->scratch);
     auto* B = A + plane_words * (size_t)n_pages;
     auto* changed = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(B) + bits_bytes);
@@ -382,7 +383,6 @@ int thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_
     const dim3 gu((unsigned)(((size_t)(wpr + 1) * height + 255) / 256), n_pages);  // one thread per aligned 32-byte block
     hipLaunchKernelGGL(k_thin_unpack, gu, dim3(256), 0, s, A, plane_words, wpr, pd, width, height);
     PRL_HIP_CHECK(hipGetLastError());
-    PRL_HIP_CHECK(hipEventRecord(ctx->last_use, s));
     return PRL_OK;
 }
 }  // namespace prl_hip
@@ -393,23 +393,11 @@ int prl_hip_thin_host(int method, const uint8_t* src, size_t src_step, int width
 {
     if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
     if (!src || !dst || src_step < (size_t)width || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    const size_t bytes = ((size_t)width * height + 255) / 256 * 256;
-    DeviceCtx* ctx = device_ctx(dev);
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);  // cached device + pinned staging (lock order: stage_mu, then mu)
-    st = ensure_stage(ctx, bytes);
-    if (st != PRL_OK) return st;
-    st = ensure_stage_pinned(ctx, bytes);
-    if (st != PRL_OK) return st;
-    uint8_t* d = static_cast<uint8_t*>(ctx->stage);
-    DrainOnExit drain_guard{nullptr};   // (direct DMA from the caller's pinned page: see prl_internal.h)
-    st = stage_upload(ctx, 0, src, src_step, (size_t)width, height, d, nullptr);
-    if (st != PRL_OK) return st;
-    st = prl_hip_thin_batch_device(method, 1, d, bytes, (size_t)width, width, height, d, bytes, (size_t)width, nullptr);
-    if (st != PRL_OK) return st;
-    return stage_download(ctx, 0, d, (size_t)width, height, dst, dst_step, nullptr);
+    const size_t row = (size_t)width;
+    return stage_host_page(src, src_step, row, height, dst, dst_step, row, height,
+                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
+                               return prl_hip_thin_batch_device(method, 1, d_in, in_bytes, row, width, height, d_out, out_bytes, row, s);
+                           });
 }
 
 }  // extern "C"

@@ -99,6 +99,106 @@ def test_no_device_means_loud_failure_not_cpu_fallback(prl):
     assert e.value.status == _capi.PRL_ERR_NO_DEVICE
 
 
+def test_entry_statuses_without_a_device(prl):
+    """The *_host entries and the batch entries on the shared device workspace check their arguments in a fixed order before
+    they look for a device: one row per rejection class (a few with two faults pin which check comes first), then valid calls,
+    which fail with PRL_ERR_NO_DEVICE here (those rows are skipped where a device is visible).  No row reaches the buffers."""
+    import torch
+    from prlib_amd import _capi as E
+
+    L = E.lib()
+    has_device = torch.cuda.is_available()
+    buf = np.zeros(1 << 16, np.uint8)
+    s, d = buf.ctypes.data, buf.ctypes.data + (1 << 15)
+    angles = (C.c_double * 2)(1.0, -2.0)
+    ang = C.addressof(angles)
+    sauvola = prl.make_params(prl.SAUVOLA, 3)   # 12 x 8 page: 11 x 7 output, 14 x 10 padded
+    even = prl.make_params(prl.SAUVOLA, 4)
+    bad_method = prl.make_params(prl.SAUVOLA, 3)
+    bad_method.method = 5
+    feng51 = prl.make_params(prl.FENG, 51)   # 12 x 8 page: the window clamps to 8, leaving no output rows
+    ps = 384   # page stride of the batch entries
+    OK, EMPTY, WIN, CH, RECT, ARG, NODEV = (E.PRL_OK, E.PRL_ERR_EMPTY, E.PRL_ERR_BAD_WINDOW, E.PRL_ERR_BAD_CHANNELS,
+                                            E.PRL_ERR_EMPTY_RECT, E.PRL_ERR_BAD_ARG, E.PRL_ERR_NO_DEVICE)
+    # (entry, arguments in order, [(changed arguments, status), ...])
+    table = [
+        (L.prl_hip_binarize_host, dict(p=C.byref(sauvola), src=s, ss=12, w=12, h=8, dst=d, ds=12, pad=None, pad_step=0), [
+            (dict(p=None), ARG), (dict(w=0), EMPTY), (dict(h=-1), EMPTY), (dict(p=C.byref(even)), WIN),
+            (dict(p=C.byref(bad_method)), ARG), (dict(p=C.byref(feng51)), RECT),
+            (dict(src=None), ARG), (dict(dst=None), ARG), (dict(ss=11), ARG), (dict(ds=10), ARG), (dict(pad=d, pad_step=13), ARG),
+            (dict(w=0, p=C.byref(even)), EMPTY), (dict(p=C.byref(even), src=None), WIN), (dict(p=C.byref(feng51), src=None), RECT),
+            (dict(), NODEV), (dict(ds=11), NODEV), (dict(pad=d, pad_step=14), NODEV)]),
+        (L.prl_hip_denoise_host, dict(c=3, strength=10.0, src=s, ss=36, w=12, h=8, dst=d, ds=36), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(c=1), CH), (dict(c=2), CH), (dict(c=5), CH),
+            (dict(src=None), ARG), (dict(dst=None), ARG), (dict(ss=35), ARG), (dict(ds=35), ARG), (dict(c=4, ds=48), ARG),
+            (dict(w=0, c=1), EMPTY), (dict(c=1, src=None), CH),
+            (dict(), NODEV), (dict(c=4, ss=48, ds=48), NODEV), (dict(h=65536), NODEV)]),
+        (L.prl_hip_thin_host, dict(m=0, src=s, ss=12, w=12, h=8, dst=d, ds=12), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(src=None), ARG), (dict(dst=None), ARG), (dict(ss=11), ARG),
+            (dict(ds=11), ARG), (dict(w=0, src=None), EMPTY),
+            (dict(), NODEV), (dict(m=1), NODEV), (dict(m=2), NODEV)]),
+        (L.prl_hip_bgnorm_host, dict(c=1, src=s, ss=12, w=12, h=8, dst=d, ds=12), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(src=None), EMPTY), (dict(c=0), CH), (dict(c=2), CH), (dict(c=5), CH),
+            (dict(dst=None), ARG), (dict(ss=11), ARG), (dict(ds=11), ARG), (dict(c=3, ss=36, ds=35), ARG),
+            (dict(c=4, ss=47, ds=36), ARG), (dict(src=None, c=2), EMPTY), (dict(c=2, dst=None), CH),
+            (dict(), NODEV), (dict(c=3, ss=36, ds=36), NODEV), (dict(c=4, ss=48, ds=36), NODEV)]),
+        (L.prl_hip_binarize_lv_host, dict(wf=1, coeff=1.0, mv=0, gamma=1.0, src=s, ss=36, w=12, h=8, dst=d, ds=12), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(src=None), EMPTY), (dict(dst=None), ARG), (dict(ss=35), ARG),
+            (dict(ds=11), ARG), (dict(src=None, dst=None), EMPTY),
+            (dict(), NODEV), (dict(wf=0), NODEV)]),
+        (L.prl_hip_bgnorm_batch_device, dict(n=1, c=1, src=s, sps=ps, ss=12, w=12, h=8, dst=d, dps=ps, ds=12, stream=None), [
+            (dict(w=0), EMPTY), (dict(c=2), CH), (dict(n=-1), ARG), (dict(src=None), ARG), (dict(dst=None), ARG),
+            (dict(ss=11), ARG), (dict(ds=11), ARG), (dict(c=3, ss=36, ds=35), ARG), (dict(h=65536), ARG),
+            (dict(w=40951, ss=40951, ds=40951), ARG), (dict(n=0), OK),
+            (dict(w=0, c=2), EMPTY), (dict(c=2, n=-1), CH), (dict(n=0, h=65536), ARG),
+            (dict(), NODEV), (dict(c=4, ss=48, ds=36), NODEV)]),
+        (L.prl_hip_binarize_lv_batch_device, dict(n=1, wf=1, coeff=1.0, mv=0, gamma=1.0, src=s, sps=ps, ss=36, w=12, h=8, dst=d,
+                                                  dps=ps, ds=12, stream=None), [
+            (dict(w=0), EMPTY), (dict(n=-1), ARG), (dict(src=None), ARG), (dict(dst=None), ARG), (dict(ss=35), ARG),
+            (dict(ds=11), ARG), (dict(h=1048561), ARG), (dict(n=0), OK), (dict(w=0, n=-1), EMPTY), (dict(n=0, h=1048561), ARG),
+            (dict(), NODEV), (dict(wf=0), NODEV), (dict(h=1048560), NODEV)]),
+        (L.prl_hip_thin_batch_device, dict(m=0, n=1, src=s, sps=ps, ss=12, w=12, h=8, dst=d, dps=ps, ds=12, stream=None), [
+            (dict(w=0), EMPTY), (dict(m=2), ARG), (dict(m=-1), ARG), (dict(n=-1), ARG), (dict(src=None), ARG),
+            (dict(dst=None), ARG), (dict(ss=11), ARG), (dict(ds=11), ARG), (dict(n=0), OK),
+            (dict(w=0, m=2), EMPTY), (dict(n=0, m=2), ARG),
+            (dict(), NODEV), (dict(m=1), NODEV), (dict(n=32769), NODEV),
+            (dict(w=1 << 21, ss=1 << 21, ds=1 << 21, h=1 << 15), NODEV)]),   # (a plane of 2^31 words: refused after the device check)
+        (L.prl_hip_morph_batch_device, dict(it=2, n=1, src=s, sps=ps, ss=12, w=12, h=8, dst=d, dps=ps, ds=12, stream=None), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(n=-1), ARG), (dict(src=None), ARG), (dict(dst=None), ARG),
+            (dict(dst=s), ARG), (dict(ss=11), ARG), (dict(ds=11), ARG), (dict(n=0), OK),
+            (dict(w=0, n=-1), EMPTY), (dict(n=0, dst=s), ARG), (dict(n=0, ss=11), ARG),
+            (dict(), NODEV), (dict(it=-8), NODEV), (dict(it=0), NODEV), (dict(it=9), NODEV), (dict(it=-12), NODEV),
+            (dict(n=32769), NODEV), (dict(it=9, n=32769), NODEV)]),
+        (L.prl_hip_nlm_planes_device, dict(n=1, c=1, h_=10.0, src=s, sps=ps, ss=12, w=12, h=8, dst=d, dps=ps, ds=12, stream=None), [
+            (dict(w=0), EMPTY), (dict(c=0), CH), (dict(c=4), CH), (dict(n=-1), ARG), (dict(src=None), ARG), (dict(dst=None), ARG),
+            (dict(dst=s), ARG), (dict(ss=11), ARG), (dict(ds=11), ARG), (dict(c=2, ss=23, ds=24), ARG), (dict(n=0), OK),
+            (dict(w=0, c=0), EMPTY), (dict(c=0, src=None), CH), (dict(n=0, dst=s), ARG),
+            (dict(), NODEV), (dict(c=2, ss=24, ds=24), NODEV), (dict(c=3, ss=36, ds=36), NODEV)]),
+        (L.prl_hip_denoise_batch_device, dict(n=1, c=3, strength=10.0, src=s, sps=ps, ss=36, w=12, h=8, dst=d, dps=ps, ds=36,
+                                              stream=None), [
+            (dict(w=0), EMPTY), (dict(c=1), CH), (dict(c=2), CH), (dict(c=5), CH), (dict(n=-1), ARG), (dict(src=None), ARG),
+            (dict(dst=None), ARG), (dict(ss=35), ARG), (dict(ds=35), ARG), (dict(c=4, ss=48), ARG), (dict(h=65536), ARG),
+            (dict(n=0), OK), (dict(w=0, c=1), EMPTY), (dict(c=1, n=-1), CH), (dict(n=0, h=65536), OK),
+            (dict(), NODEV), (dict(c=4, ss=48, ds=48), NODEV), (dict(n=65536), NODEV)]),
+        (L.prl_hip_rotate_batch_device, dict(n=1, c=1, ang=ang, src=s, sps=ps, ss=12, w=12, h=8, dst=d, dps=ps, ds=12, stream=None), [
+            (dict(w=0), EMPTY), (dict(c=0), CH), (dict(c=5), CH), (dict(n=-1), ARG), (dict(ang=None), ARG), (dict(src=None), ARG),
+            (dict(dst=None), ARG), (dict(dst=s), ARG), (dict(ss=11), ARG), (dict(w=32768, ss=32768), ARG), (dict(h=32768), ARG),
+            (dict(n=0), OK), (dict(w=0, c=0), EMPTY), (dict(c=0, ang=None), CH), (dict(n=0, h=32768), ARG),
+            (dict(), NODEV), (dict(c=4, ss=48, ds=48), NODEV), (dict(ds=1), NODEV)]),   # (dst_step: checked per chunk, after the device)
+    ]
+    wrong = []
+    for fn, args, cases in table:
+        for change, want in cases:
+            if want == NODEV and has_device:
+                continue
+            assert set(change) <= set(args), (fn.__name__, change)
+            got = fn(*{**args, **change}.values())
+            if got != want:
+                wrong.append((fn.__name__, change, got, want))
+    assert not wrong, wrong
+    assert not buf.any()
+
+
 def test_product_does_not_reference_the_oracle():
     """The oracle is test infrastructure: nothing under prlib_amd/ may import, include or link it."""
     bad = []
