@@ -1,0 +1,7 @@
+// binarizeAGT.h - drop-in for PRLib's header of the same name (src/binarizations/binarizeAGT.h:32): declares
+// prl::binarizeAGT with the reference's signature and CV_EXPORTS linkage.  A caller that includes "binarizeAGT.h" builds
+// against this repository with only its include path changed to include/prl; the declarations themselves live in prl.h.
+#ifndef PRLIB_HIP_DROPIN_binarizeAGT_h
+#define PRLIB_HIP_DROPIN_binarizeAGT_h
+#include "prl.h"
+#endif  // PRLIB_HIP_DROPIN_binarizeAGT_h

@@ -382,6 +382,63 @@ int prl_hip_median_batch_device(int n_pages, int channels, int ksize, size_t tim
 int prl_hip_median_host(int channels, int ksize, size_t times, const uint8_t* src, size_t src_step, int width, int height,
                         uint8_t* dst, size_t dst_step);
 
+/* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
+
+#define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */
+#define PRL_ADAPTIVE_GAUSSIAN_C 1  /* cv::ADAPTIVE_THRESH_GAUSSIAN_C */
+#define PRL_THRESH_BINARY 0        /* cv::THRESH_BINARY */
+#define PRL_THRESH_BINARY_INV 1    /* cv::THRESH_BINARY_INV */
+
+/*
+ * cv::adaptiveThreshold(src, dst, max_value, method, type, block_size, delta) on 8-bit gray pages in device memory.
+ * M = the block_size x block_size local mean around a pixel (BORDER_REPLICATE): MEAN_C the integer block sum times
+ * 1.0 / block_size^2 in float64, rounded half to even; GAUSSIAN_C a separable float32 Gaussian of the float32 page in
+ * OpenCV's tap order, rounded half to even.  on = p - M > -idelta with idelta = ceil(delta) for BINARY and
+ * floor(delta) for BINARY_INV; BINARY writes on ? imax : 0, BINARY_INV on ? 0 : imax, imax = saturate_u8(cvRound(max_value));
+ * max_value < 0 gives 0 everywhere.  auto_invert != 0 adds the last step of prl::binarizeNativeAdaptive
+ * (binarizeNativeAdaptive.cpp:108-111): a page whose mask has a mean below 128 becomes 255 - mask (decided per page, applied
+ * while the mask is written).  block_size: odd, 3 .. 255.  Sizes: width, height <= 32768.  Source and destination must not
+ * overlap.  Enqueues on `stream`, no synchronisation.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_WINDOW (block_size
+ * < 3, even or > 255); PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row bytes, size above the limit, unknown method
+ * or type, NaN max_value or delta, overlapping source and destination).
+ */
+int prl_hip_adaptive_threshold_batch_device(int n_pages, int method, int type, double max_value, int block_size, double delta,
+                                            int auto_invert, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                            int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                            void* stream);
+int prl_hip_adaptive_threshold_host(int method, int type, double max_value, int block_size, double delta, int auto_invert,
+                                    const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+
+/* The reference's functions on top of it, device resident: [BGR -> gray], [cv::medianBlur], cv::adaptiveThreshold, [flip]. */
+typedef struct prl_adaptive_params {
+    int median_ksize;     /* cv::medianBlur's window, odd >= 3; 0 or 1: no median (binarizePureAdaptiveGaussian) */
+    int median_on_color;  /* 0: gray first, then the median (binarizeNativeAdaptive.cpp:60-73); != 0: the median on the colour
+                             page, then gray (binarizeAT.cpp:45-54, binarizeAGT.cpp:45-52) */
+    int method;           /* PRL_ADAPTIVE_MEAN_C / PRL_ADAPTIVE_GAUSSIAN_C */
+    int type;             /* PRL_THRESH_BINARY / PRL_THRESH_BINARY_INV */
+    double max_value;
+    int block_size;       /* odd, 3 .. 255 (the reference's "automatic" size is the caller's: (int)(sqrt(rows^2 + cols^2) / 333 + 7)) */
+    int auto_invert;      /* != 0: 255 - mask where the mask's mean is below 128 */
+    double delta;
+} prl_adaptive_params;
+
+/* prl::binarizeNativeAdaptive's header defaults (binarizeNativeAdaptive.h:62-74): median 5, gray first, GAUSSIAN_C,
+ * BINARY_INV, 255, block 19, shift 9, auto-invert. */
+void prl_hip_default_adaptive_params(prl_adaptive_params* out);
+
+/*
+ * Pages of 1, 3 or 4 interleaved channels -> width x height byte masks.  The intermediates (gray page, median result, bit
+ * plane of the undecided mask) live in the device's cached scratch; the stages are ordered by `stream` alone.
+ * Order of the checks: PRL_ERR_EMPTY; PRL_ERR_BAD_ARG for params == NULL; PRL_ERR_BAD_WINDOW (block_size, then median_ksize
+ * negative or even); PRL_ERR_BAD_CHANNELS (not 1, 3 or 4); PRL_ERR_BAD_ARG as above (median_ksize > 65535 included).
+ */
+int prl_hip_binarize_adaptive_batch_device(const prl_adaptive_params* params, int n_pages, int channels, const uint8_t* d_src,
+                                           size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                           size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_binarize_adaptive_host(const prl_adaptive_params* params, int channels, const uint8_t* src, size_t src_step, int width,
+                                   int height, uint8_t* dst, size_t dst_step);
+
 /* ---- local-variance binarizers ------------------------------------------------------------- */
 
 /*

@@ -53,6 +53,8 @@ EXPORTED_SYMBOLS = [
     "prl_hip_binarize_batch_host", "prl_hip_page_range", "prl_hip_binarize_lv_batch_device", "prl_hip_binarize_lv_host",
     "prl_hip_chain_batch_host", "prl_hip_alloc_host", "prl_hip_free_host", "prl_hip_host_register", "prl_hip_host_unregister",
     "prl_hip_median_batch_device", "prl_hip_median_host",
+    "prl_hip_adaptive_threshold_batch_device", "prl_hip_adaptive_threshold_host", "prl_hip_default_adaptive_params",
+    "prl_hip_binarize_adaptive_batch_device", "prl_hip_binarize_adaptive_host",
 ]
 
 
@@ -77,6 +79,13 @@ class ChainParams(C.Structure):
 
     _fields_ = [("denoise", C.c_int32), ("denoise_strength", C.c_float), ("binarize", BinarizeParams), ("thin", C.c_int32),
                 ("deskew", C.c_int32), ("background_normalization", C.c_int32)]
+
+
+class AdaptiveParams(C.Structure):
+    """struct prl_adaptive_params."""
+
+    _fields_ = [("median_ksize", C.c_int32), ("median_on_color", C.c_int32), ("method", C.c_int32), ("type", C.c_int32),
+                ("max_value", C.c_double), ("block_size", C.c_int32), ("auto_invert", C.c_int32), ("delta", C.c_double)]
 
 
 class BinarizeGeometry(C.Structure):
@@ -174,6 +183,13 @@ def lib() -> C.CDLL:
         L.prl_hip_binarize_lv_host.argtypes = [i, C.c_double, i, C.c_double, vp, sz, i, i, vp, sz]
         L.prl_hip_median_batch_device.argtypes = [i, i, i, sz, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_median_host.argtypes = [i, i, sz, vp, sz, i, i, vp, sz]
+        d = C.c_double
+        L.prl_hip_adaptive_threshold_batch_device.argtypes = [i, i, i, d, i, d, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_adaptive_threshold_host.argtypes = [i, i, d, i, d, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_default_adaptive_params.argtypes = [P(AdaptiveParams)]
+        L.prl_hip_default_adaptive_params.restype = None
+        L.prl_hip_binarize_adaptive_batch_device.argtypes = [P(AdaptiveParams), i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_binarize_adaptive_host.argtypes = [P(AdaptiveParams), i, vp, sz, i, i, vp, sz]
         _lib = L
     return _lib
 

@@ -387,6 +387,13 @@ bool ranges_overlap(const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b
 
 }  // namespace
 
+// one pass over pages that the caller owns (adaptive.hip; the source is not the destination, the caller holds the device)
+int median_pass_pages(int width, int height, int channels, int ksize, const PageSet& src, const PageSetOut& dst, int n_pages,
+                      hipStream_t stream)
+{
+    return median_pass(med_geom(width, height, channels, ksize), env_knobs().median_generic, src, dst, n_pages, stream);
+}
+
 }  // namespace prl_hip
 
 using namespace prl_hip;

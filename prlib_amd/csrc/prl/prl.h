@@ -10,6 +10,9 @@
 //   src/binarizations/binarizeFeng.h:46-53                 prl::binarizeFeng
 //   src/denoise/denoiseNLM.h:32                            prl::denoise
 //   src/denoise/denoiseSaltPepper.h:40                     prl::denoiseSaltPepper
+//   src/binarizations/binarizeNativeAdaptive.h:62-74       prl::binarizeNativeAdaptive
+//   src/binarizations/binarizeAT.h:33, binarizeAGT.h:32    prl::binarizeAT, prl::binarizeAGT
+//   src/binarizations/binarizePureAdaptiveGaussian.h:33    prl::binarizePureAdaptiveGaussian
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -63,6 +66,33 @@ CV_EXPORTS void denoise(const cv::Mat& inputImage, cv::Mat& outputImage, double 
 // channels (OpenCV also takes 16U / 16S / 32F at k <= 5: not here).  The output is a new continuous Mat; the input's pixels
 // are never written (out may be in, or a view of it).
 CV_EXPORTS void denoiseSaltPepper(const cv::Mat& in, cv::Mat& out, int kernelSize, size_t times);
+
+// src/binarizations/binarizeNativeAdaptive.h:62-74 - [BGR -> gray], cv::medianBlur, cv::adaptiveThreshold(THRESH_BINARY_INV),
+// 255 - mask where the mask's mean is below 128 (.cpp:34-135), in the reference's statement order: std::invalid_argument for an
+// empty input, then for a max value outside [0; 255] (NaN included); a colour input becomes gray in the caller's Mat (:60; not
+// with PRL_KEEP_INPUT); cv::Exception(StsAssert) for medianBlurKernelSize < 3 or even; adaptiveThresholdingBlockSize < 3 means
+// (int)(sqrt(rows^2 + cols^2) / 333 + 7), and an even block size is cv::adaptiveThreshold's StsAssert (a 4096 x 4096 page gives
+// 24).  Not provided, cv::Exception(StsNotImplemented) after the reference's own checks: isGaussianBlurReqiured (OpenCV's 8-bit
+// fixed-point GaussianBlur), bilateralFilterBlockSize >= 3 (outputImage then already holds the mask), block sizes above 255.
+// Where the block size is rejected outputImage stays untouched (the reference leaves the median-filtered page there).
+CV_EXPORTS void binarizeNativeAdaptive(cv::Mat& inputImage, cv::Mat& outputImage, bool isGaussianBlurReqiured = 0,
+                            int medianBlurKernelSize = 5, int GaussianBlurKernelSize = 7, double GaussianBlurSigma = 150.0,
+                            bool isAdaptiveThresholdCalculatedByGaussian = true, double adaptiveThresholdingMaxValue = 255.0,
+                            int adaptiveThresholdingBlockSize = 19, double adaptiveThresholdingShift = 9,
+                            int bilateralFilterBlockSize = 0, double bilateralFilterColorSigma = 150.0,
+                            double bilateralFilterSpaceSigma = 150.0);
+
+// src/binarizations/binarizeAT.h:33, binarizeAGT.h:32, binarizePureAdaptiveGaussian.h:33 - cv::medianBlur on the COLOUR page
+// (AT, AGT), BGR -> gray, cv::adaptiveThreshold(MEAN_C for AT / GAUSSIAN_C for the others, THRESH_BINARY).  std::invalid_argument
+// for an empty input; cv::medianBlur's checks (odd kernel; 1 = no filter); a 1-channel input is cv::Exception(StsAssert) with
+// outputImage untouched: the reference hands cv::adaptiveThreshold an empty Mat there (binarizeAT.cpp:56-65); an even or
+// < 3 block size is StsAssert.  The input is never written.
+CV_EXPORTS void binarizeAT(const cv::Mat& inputImage, cv::Mat& outputImage, const int medianKernelSize, const double maxValue,
+                const int blockSize, const int shift);
+CV_EXPORTS void binarizeAGT(const cv::Mat& inputImage, cv::Mat& outputImage, const int medianKernelSize, const double maxValue,
+                 const int blockSize, const int shift);
+CV_EXPORTS void binarizePureAdaptiveGaussian(const cv::Mat& inputImage, cv::Mat& outputImage, const double maxValue,
+                                  const int blockSize, const int shift);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

@@ -5,6 +5,7 @@
 // (tests/cpp/opencv_api/).  With OpenCV present the colour conversion is OpenCV's own cv::cvtColor, as in the reference.
 #include "prl.h"
 
+#include <cmath>
 #include <cstring>
 #include <stdexcept>
 #include <string>
@@ -181,6 +182,128 @@ void prl::denoiseSaltPepper(const cv::Mat& in, cv::Mat& out, int kernelSize, siz
         raise(st);
     }
     out = result;
+}
+
+namespace {
+
+constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255
+
+// cv::medianBlur's own checks ([upstream] OpenCV >= 4), as prl::denoiseSaltPepper states them
+void median_checks(const cv::Mat& in, int ksize, const char* func, int line)
+{
+    if (ksize % 2 != 1) fail_cv(cv::Error::StsAssert, "(ksize % 2 == 1) && (_src0.dims() <= 2 )", func, line);
+    if (in.depth() != CV_8U || in.channels() > 4)
+        fail_cv(cv::Error::StsUnsupportedFormat, "prl: cv::medianBlur on 8-bit images of 1..4 channels only", func, line);
+    if (in.channels() == 2 && ksize >= 7) fail_cv(cv::Error::StsAssert, "cn == 1 || cn == 3 || cn == 4", func, line);
+}
+
+// cv::adaptiveThreshold's CV_Assert( blockSize % 2 == 1 && blockSize > 1 ), then this library's own limit
+void block_checks(int blockSize, const char* func, int line)
+{
+    if (!(blockSize % 2 == 1 && blockSize > 1)) fail_cv(cv::Error::StsAssert, "blockSize % 2 == 1 && blockSize > 1", func, line);
+    if (blockSize > kAdaptiveMaxBlock)
+        fail_cv(cv::Error::StsNotImplemented, "prl: cv::adaptiveThreshold with a block size above 255 is not provided", func, line);
+}
+
+void adaptive_call(const prl_adaptive_params& p, const cv::Mat& in, cv::Mat& out, const char* func, int line)
+{
+    cv::Mat result(in.rows, in.cols, CV_8UC1);
+    const int st = prl_hip_binarize_adaptive_host(&p, in.channels(), in.data, in.step, in.cols, in.rows, result.data, result.step);
+    if (st != PRL_OK) raise_at(st, func, line);
+    out = result;
+}
+
+// binarizeAT.cpp:33-68, binarizeAGT.cpp:33-60 (median != 0), binarizePureAdaptiveGaussian.cpp:32-75 (median == 0)
+void at_impl(const cv::Mat& in, cv::Mat& out, bool with_median, int medianKernelSize, int method, double maxValue, int blockSize,
+             int shift, const char* func)
+{
+    if (in.empty()) throw std::invalid_argument("Input image for binarization is empty");
+    if (with_median) median_checks(in, medianKernelSize, func, __LINE__);
+    else if (in.depth() != CV_8U) fail_cv(cv::Error::StsUnsupportedFormat, "prl: 8-bit images only", func, __LINE__);
+    // 1 channel: the reference hands an EMPTY Mat to cv::adaptiveThreshold (binarizeAT.cpp:56-65); [upstream] OpenCV >= 4
+    // asserts on it.  outputImage stays as it was.
+    if (in.channels() == 1) fail_cv(cv::Error::StsAssert, "!_src.empty()", func, __LINE__);
+    if (in.channels() != 3 && in.channels() != 4) raise_at(PRL_ERR_BAD_CHANNELS, func, __LINE__);   // cv::cvtColor(BGR2GRAY)
+    block_checks(blockSize, func, __LINE__);
+    prl_adaptive_params p{};
+    p.median_ksize = with_median ? medianKernelSize : 0;
+    p.median_on_color = 1;
+    p.method = method;
+    p.type = PRL_THRESH_BINARY;
+    p.max_value = maxValue;
+    p.block_size = blockSize;
+    p.delta = (double)shift;
+    p.auto_invert = 0;
+    adaptive_call(p, in, out, func, __LINE__);
+}
+
+}  // namespace
+
+// binarizeNativeAdaptive.cpp:34-135 in the reference's statement order.
+void prl::binarizeNativeAdaptive(cv::Mat& inputImage, cv::Mat& outputImage, bool isGaussianBlurReqiured, int medianBlurKernelSize,
+                                 int GaussianBlurKernelSize, double GaussianBlurSigma, bool isAdaptiveThresholdCalculatedByGaussian,
+                                 double adaptiveThresholdingMaxValue, int adaptiveThresholdingBlockSize,
+                                 double adaptiveThresholdingShift, int bilateralFilterBlockSize, double bilateralFilterColorSigma,
+                                 double bilateralFilterSpaceSigma)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image for binarization is empty");
+    if (!(adaptiveThresholdingMaxValue >= 0 && adaptiveThresholdingMaxValue <= 255))
+        throw std::invalid_argument("Max value must be in range [0; 255]");
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl: 8-bit images only");
+    if (inputImage.channels() > 1) {
+        if (inputImage.channels() != 3 && inputImage.channels() != 4) raise(PRL_ERR_BAD_CHANNELS);
+#ifndef PRL_KEEP_INPUT
+        bgr2gray_inplace(inputImage);   // cv::cvtColor(inputImage, inputImage, cv::COLOR_BGR2GRAY) - :60
+#endif
+    }
+    if (!isGaussianBlurReqiured) {
+        if (!(medianBlurKernelSize >= 3)) PRL_FAIL_CV(cv::Error::StsAssert, "medianBlurKernelSize >= 3");
+        median_checks(inputImage, medianBlurKernelSize, __func__, __LINE__);
+    } else {
+        if (!(GaussianBlurKernelSize >= 3)) PRL_FAIL_CV(cv::Error::StsAssert, "GaussianBlurKernelSize >= 3");
+        if (!(GaussianBlurSigma > 0)) PRL_FAIL_CV(cv::Error::StsAssert, "GaussianBlurSigma > 0");
+        PRL_FAIL_CV(cv::Error::StsNotImplemented,
+                    "prl::binarizeNativeAdaptive with isGaussianBlurReqiured needs OpenCV's 8-bit fixed-point cv::GaussianBlur, which this library does not provide");
+    }
+    if (adaptiveThresholdingBlockSize < 3) {
+        const double diagonal = std::sqrt((double)(inputImage.rows * inputImage.rows + inputImage.cols * inputImage.cols));
+        adaptiveThresholdingBlockSize = static_cast<int>(diagonal / 333 + 7);   // may be even: cv::adaptiveThreshold then throws
+    }
+    block_checks(adaptiveThresholdingBlockSize, __func__, __LINE__);
+    prl_adaptive_params p{};
+    p.median_ksize = medianBlurKernelSize;
+    p.median_on_color = 0;
+    p.method = isAdaptiveThresholdCalculatedByGaussian ? PRL_ADAPTIVE_GAUSSIAN_C : PRL_ADAPTIVE_MEAN_C;
+    p.type = PRL_THRESH_BINARY_INV;
+    p.max_value = adaptiveThresholdingMaxValue;
+    p.block_size = adaptiveThresholdingBlockSize;
+    p.delta = adaptiveThresholdingShift;
+    p.auto_invert = 1;
+    adaptive_call(p, inputImage, outputImage, __func__, __LINE__);
+    if (bilateralFilterBlockSize >= 3) {   // outputImage holds the mask, as in the reference (:113-133)
+        if (bilateralFilterColorSigma <= 0) throw std::invalid_argument("Color sigma for bilateral filtration must be greater than 0");
+        if (bilateralFilterSpaceSigma <= 0) throw std::invalid_argument("Space sigma for bilateral filtration must be greater than 0");
+        PRL_FAIL_CV(cv::Error::StsNotImplemented,
+                    "prl::binarizeNativeAdaptive with bilateralFilterBlockSize >= 3 needs cv::bilateralFilter, which this library does not provide");
+    }
+}
+
+void prl::binarizeAT(const cv::Mat& inputImage, cv::Mat& outputImage, const int medianKernelSize, const double maxValue,
+                     const int blockSize, const int shift)
+{
+    at_impl(inputImage, outputImage, true, medianKernelSize, PRL_ADAPTIVE_MEAN_C, maxValue, blockSize, shift, __func__);
+}
+
+void prl::binarizeAGT(const cv::Mat& inputImage, cv::Mat& outputImage, const int medianKernelSize, const double maxValue,
+                      const int blockSize, const int shift)
+{
+    at_impl(inputImage, outputImage, true, medianKernelSize, PRL_ADAPTIVE_GAUSSIAN_C, maxValue, blockSize, shift, __func__);
+}
+
+void prl::binarizePureAdaptiveGaussian(const cv::Mat& inputImage, cv::Mat& outputImage, const double maxValue, const int blockSize,
+                                       const int shift)
+{
+    at_impl(inputImage, outputImage, false, 0, PRL_ADAPTIVE_GAUSSIAN_C, maxValue, blockSize, shift, __func__);
 }
 
 namespace {

@@ -370,6 +370,10 @@ int chain_pass_layout(const prl_chain_params* cp, int n_pages, int channels, int
                       size_t* per_page_out, size_t* desk_page_out);
 void host_slots_free(DeviceCtx* ctx);  // host_batch.hip: the pinned bounce slots of prl_hip_chain_batch_host (caller holds host_mu)
 
+// ---- median (median.hip): one cv::medianBlur pass, odd ksize >= 3, source and destination distinct; enqueues only ----------
+int median_pass_pages(int width, int height, int channels, int ksize, const PageSet& src, const PageSetOut& dst, int n_pages,
+                      hipStream_t stream);
+
 // ---- morphology (morph.hip) ------------------------------------------------------------------
 int morph_run(int iterations, const PageSet& src, int n_pages, int width, int height,
               const PageSetOut& dst, hipStream_t stream);
