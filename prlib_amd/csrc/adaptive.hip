@@ -373,13 +373,10 @@ int prl_hip_binarize_adaptive_batch_device(const prl_adaptive_params* p, int n_p
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
         const uint8_t* s0 = d_src + (size_t)first * src_page_stride;
-        PageSet cur{};
-        cur.base = s0; cur.page_stride = src_page_stride; cur.step = src_step;
-        PageSetOut ga{};
-        ga.base = G; ga.page_stride = gray; ga.step = (size_t)width;
+        PageSet cur = page_set(s0, src_page_stride, src_step);
+        const PageSetOut ga = page_set_out(G, gray, (size_t)width);
         if (med_color) {   // binarizeAT.cpp / binarizeAGT.cpp: medianBlur on the colour page, then cvtColor
-            PageSetOut a{};
-            a.base = A; a.page_stride = a_bytes; a.step = R;
+            const PageSetOut a = page_set_out(A, a_bytes, R);
             st = median_pass_pages(width, height, channels, p->median_ksize, cur, a, cnt, hs);
             if (st != PRL_OK) return st;
             st = prl_hip_bgr2gray_batch_device(cnt, channels, A, a_bytes, R, width, height, G, gray, (size_t)width, stream);
@@ -390,8 +387,7 @@ int prl_hip_binarize_adaptive_batch_device(const prl_adaptive_params* p, int n_p
                                                stream);
             if (st != PRL_OK) return st;
             if (med) {
-                PageSet a{};
-                a.base = A; a.page_stride = gray; a.step = (size_t)width;
+                const PageSet a = page_set(A, gray, (size_t)width);
                 st = median_pass_pages(width, height, 1, p->median_ksize, a, ga, cnt, hs);
                 if (st != PRL_OK) return st;
             }
@@ -402,8 +398,7 @@ int prl_hip_binarize_adaptive_batch_device(const prl_adaptive_params* p, int n_p
         if (med || color) {
             cur.base = G; cur.page_stride = gray; cur.step = (size_t)width;
         }
-        PageSetOut d{};
-        d.base = d_dst + (size_t)first * dst_page_stride; d.page_stride = dst_page_stride; d.step = dst_step;
+        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
         st = adaptive_run(sp, width, height, cur, d, cnt, work, hs);
         if (st != PRL_OK) return st;
     }

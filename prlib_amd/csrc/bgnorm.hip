@@ -364,10 +364,8 @@ int prl_hip_bgnorm_batch_device(int n_pages, int channels, const uint8_t* d_src,
     if (st != PRL_OK) return st;
     DeviceRelease release{ctx, hs};
     for (int first = 0; first < n_pages; first += chunk) {
-        PageSet s{};
-        s.base = d_src + (size_t)first * src_page_stride; s.page_stride = src_page_stride; s.step = src_step;
-        PageSetOut d{};
-        d.base = d_dst + (size_t)first * dst_page_stride; d.page_stride = dst_page_stride; d.step = dst_step;
+        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
+        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
         st = bgnorm_run(std::min(chunk, n_pages - first), channels, s, width, height, d, ctx->scratch, hs);
         if (st != PRL_OK) return st;
     }

@@ -32,6 +32,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "prl_device_math.h"
 #include "prl_internal.h"
@@ -2133,27 +2134,91 @@ __global__ void __launch_bounds__(256) k_page_min_border(PageSet src, int width,
     if ((threadIdx.x & (kWave - 1)) == 0 && mn < 255u) atomicMin(&g[page].imin, (int)mn);
 }
 
+// The carved work area (work_area) and the launch state of one fused_run call.
+struct FusedLaunch {
+    unsigned* cnt = nullptr;     // counter block: [1] fix-up-list length, [2] Wolf candidate-list length, [5] pages of the page-major corner kernel, [60] epilogue arrivals; words 64 ...: the refine queue's bucket counters (kRefCounterStride apart)
+    RefItem* rl = nullptr;       // refine list: kRefBuckets x kRefBucketCap
+    WorkItem* wl = nullptr;      // fix-up list
+    WorkItem* cand = nullptr;    // Wolf candidate list
+    CornerAcc* acc = nullptr;    // corner sums
+    float* segmax = nullptr;     // Wolf per-wavefront maxima (FusedParams::segmax)
+    unsigned* done = nullptr;    // arrivals per queued pixel
+    CornerAcc* cacc = nullptr;   // corner sums of Wolf-Jolion's candidates
+    GroupArrays ga{};            // k_group_items: item indices by page, page starts / cursors / list
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // optional: recorded around the threshold sweep
+    hipEvent_t before_refine = nullptr;                 // Wolf-Jolion: the literal k / devianceMax of the side stream
+    int sh = 0;                  // (w - 1) & 7
+    int n_pages = 0;
+};
+
+// One walk over the blocks of the fused work area, in their order in memory (plain sizes, no per-block rounding): the pointers
+// for a call (`base` = the area), and the end offset = the bytes the area needs (fused_small_bytes; `base` may be null then).
+static size_t work_area(uint8_t* base, int n_pages, FusedLaunch* L)
+{
+    size_t off = 0;
+    auto take = [&](auto** p, size_t count) {
+        using T = std::remove_pointer_t<std::remove_pointer_t<decltype(p)>>;
+        *p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+        off += sizeof(T) * count;
+    };
+    const size_t n = (size_t)std::max(n_pages, 1);
+    take(&L->cnt, kFusedCounterBytes / sizeof(unsigned));
+    take(&L->rl, (size_t)kRefineCap);
+    take(&L->wl, (size_t)kWorkCap);
+    take(&L->cand, (size_t)kWorkCap);
+    take(&L->acc, (size_t)kWorkCap);
+    take(&L->segmax, (size_t)kSegmaxCap);
+    take(&L->done, (size_t)kWorkCap);
+    take(&L->cacc, (size_t)kWorkCap);
+    take(&L->ga.sidx, (size_t)kWorkCap);
+    take(&L->ga.pstart, n + 1);
+    take(&L->ga.pcur, n);
+    take(&L->ga.plist, n + 3);
+    return off;
+}
+
+// f(std::integral_constant<int, SH>) for sh = (w - 1) & 7 of an odd window
+template <typename F>
+int with_sh(int sh, F&& f)
+{
+    switch (sh) {
+    case 0: return f(std::integral_constant<int, 0>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    default: return PRL_ERR_BAD_ARG;
+    }
+}
+
+// f(std::integral_constant<int, METHOD>) for the methods of the general path (Wolf-Jolion has its own schedule)
+template <typename F>
+int with_method(int method, F&& f)
+{
+    switch (method) {
+    case PRL_SAUVOLA: return f(std::integral_constant<int, PRL_SAUVOLA>{});
+    case PRL_NIBLACK: return f(std::integral_constant<int, PRL_NIBLACK>{});
+    case PRL_NICK: return f(std::integral_constant<int, PRL_NICK>{});
+    case PRL_FENG: return f(std::integral_constant<int, PRL_FENG>{});
+    default: return PRL_ERR_BAD_ARG;
+    }
+}
+
 template <int METHOD>
-int launch_sweep(int sh, hipStream_t stream, const PageSet& src, const PageSetOut& dst, const FusedParams& fp,
-                 PageGlobals* g, RefItem* rl, WorkItem* cand, unsigned* cnt)
+int launch_sweep(const FusedLaunch& L, const FusedCall& c, const FusedParams& fp, hipStream_t stream)
 {
     if constexpr (METHOD == PRL_SAUVOLA || METHOD == PRL_NIBLACK || METHOD == PRL_NICK || METHOD == PRL_WOLFJOLION || METHOD == PRL_FENG) {
         // windows of 33 .. 129 columns: float window rows, integer horizontal Q sums (k_fused_q); typed loads address a page with
         // 32-bit offsets
         const int n1 = fp.tp.w - 1;
         if (env_knobs().fused_qint && env_knobs().flt && !fp.flt && n1 > 30 && n1 <= 128 && !(n1 & 1) &&
-            (unsigned long long)src.step * (unsigned long long)fp.tp.height < 0x7fffffffull) {
+            (unsigned long long)c.src.step * (unsigned long long)fp.tp.height < 0x7fffffffull) {
             const dim3 grid(8u * fp.xcd_waves), block(64);
             const int ef = env_knobs().fused_qint >= 2 ? 1 : 0;
-            switch (sh) {
-            case 0: hipLaunchKernelGGL((k_fused_q<METHOD, 0>), grid, block, 0, stream, src, dst, fp, g, rl, cand, cnt, ef); break;
-            case 2: hipLaunchKernelGGL((k_fused_q<METHOD, 2>), grid, block, 0, stream, src, dst, fp, g, rl, cand, cnt, ef); break;
-            case 4: hipLaunchKernelGGL((k_fused_q<METHOD, 4>), grid, block, 0, stream, src, dst, fp, g, rl, cand, cnt, ef); break;
-            case 6: hipLaunchKernelGGL((k_fused_q<METHOD, 6>), grid, block, 0, stream, src, dst, fp, g, rl, cand, cnt, ef); break;
-            default: return PRL_ERR_BAD_ARG;
-            }
-            PRL_HIP_CHECK(hipGetLastError());
-            return PRL_OK;
+            return with_sh(L.sh, [&](auto shv) {
+                hipLaunchKernelGGL((k_fused_q<METHOD, shv.value>), grid, block, 0, stream, c.src, c.dst, fp, c.d_globals, L.rl, L.cand, L.cnt, ef);
+                PRL_HIP_CHECK(hipGetLastError());
+                return PRL_OK;
+            });
         }
     }
     // wavefronts are independent; one per workgroup schedules best (256 x 4K pages: 4 per workgroup 4.38 ms, 2: 4.18,
@@ -2164,73 +2229,55 @@ int launch_sweep(int sh, hipStream_t stream, const PageSet& src, const PageSetOu
     const unsigned blocks = 8u * ((fp.xcd_waves + wpb - 1) / wpb);   // each XCD: its share of every tier
     const dim3 grid(blocks), block(64 * wpb);
     const bool wide = fp.tp.w - 1 > 181;  // S no longer fits the mantissa of 2^23 (eval32)
-#define PRL_LAUNCH_FUSED(SHV)                                                                                    \
-    do {                                                                                                         \
-        if (wide)                                                                                                \
-            hipLaunchKernelGGL((k_fused<METHOD, SHV, true>), grid, block, 0, stream, src, dst, fp, g, rl, cand, cnt);    \
-        else                                                                                                     \
-            hipLaunchKernelGGL((k_fused<METHOD, SHV, false>), grid, block, 0, stream, src, dst, fp, g, rl, cand, cnt);   \
-    } while (0)
-    switch (sh) {
-    case 0: PRL_LAUNCH_FUSED(0); break;
-    case 2: PRL_LAUNCH_FUSED(2); break;
-    case 4: PRL_LAUNCH_FUSED(4); break;
-    case 6: PRL_LAUNCH_FUSED(6); break;
-    default: return PRL_ERR_BAD_ARG;
-    }
-#undef PRL_LAUNCH_FUSED
-    PRL_HIP_CHECK(hipGetLastError());
-    return PRL_OK;
+    return with_sh(L.sh, [&](auto shv) {
+        if (wide)
+            hipLaunchKernelGGL((k_fused<METHOD, shv.value, true>), grid, block, 0, stream, c.src, c.dst, fp, c.d_globals, L.rl, L.cand, L.cnt);
+        else
+            hipLaunchKernelGGL((k_fused<METHOD, shv.value, false>), grid, block, 0, stream, c.src, c.dst, fp, c.d_globals, L.rl, L.cand, L.cnt);
+        PRL_HIP_CHECK(hipGetLastError());
+        return PRL_OK;
+    });
 }
 
 // the threshold sweep of a flagged page's second chance (k_fused_exact)
 template <int METHOD>
-int launch_sweep_exact(int sh, hipStream_t stream, const PageSet& src, const PageSetOut& dst, const FusedParams& fp, PageGlobals* g,
-                       unsigned* cnt, WorkItem* wl, CornerAcc* acc, unsigned* done)
+int launch_sweep_exact(const FusedLaunch& L, const FusedCall& c, const FusedParams& fp)
 {
     const unsigned blocks = 8u * fp.xcd_waves;
     const dim3 grid(blocks), block(64);
     const bool wide = fp.tp.w - 1 > 181;
-#define PRL_LAUNCH_EXACT(SHV)                                                                                                  \
-    do {                                                                                                                       \
-        if (wide) hipLaunchKernelGGL((k_fused_exact<METHOD, SHV, true>), grid, block, 0, stream, src, dst, fp, g, cnt, wl, acc, done);   \
-        else hipLaunchKernelGGL((k_fused_exact<METHOD, SHV, false>), grid, block, 0, stream, src, dst, fp, g, cnt, wl, acc, done);       \
-    } while (0)
-    switch (sh) {
-    case 0: PRL_LAUNCH_EXACT(0); break;
-    case 2: PRL_LAUNCH_EXACT(2); break;
-    case 4: PRL_LAUNCH_EXACT(4); break;
-    case 6: PRL_LAUNCH_EXACT(6); break;
-    default: return PRL_ERR_BAD_ARG;
-    }
-#undef PRL_LAUNCH_EXACT
-    PRL_HIP_CHECK(hipGetLastError());
-    return PRL_OK;
+    return with_sh(L.sh, [&](auto shv) {
+        if (wide)
+            hipLaunchKernelGGL((k_fused_exact<METHOD, shv.value, true>), grid, block, 0, c.stream, c.src, c.dst, fp, c.d_globals, L.cnt, L.wl, L.acc, L.done);
+        else
+            hipLaunchKernelGGL((k_fused_exact<METHOD, shv.value, false>), grid, block, 0, c.stream, c.src, c.dst, fp, c.d_globals, L.cnt, L.wl, L.acc, L.done);
+        PRL_HIP_CHECK(hipGetLastError());
+        return PRL_OK;
+    });
 }
 
+// threshold sweep, k_refine, literal fix-up on the caller's stream
 template <int METHOD>
-int launch_fused(int sh, hipStream_t stream, const PageSet& src, const PageSetOut& dst, const FusedParams& fp,
-                 PageGlobals* g, RefItem* rl, WorkItem* wl, WorkItem* cand, CornerAcc* acc, unsigned* cnt,
-                 hipEvent_t ev_start, hipEvent_t ev_stop, int n_pages, const GroupArrays& ga,
-                 hipEvent_t before_refine = nullptr, CornerAcc* cacc = nullptr, bool exact = false)
+int launch_fused(const FusedLaunch& L, const FusedCall& c, const FusedParams& fp)
 {
-    unsigned* done = reinterpret_cast<unsigned*>(fp.segmax + kSegmaxCap);  // arrivals per queued pixel (see fused_small_bytes)
-    if (ev_start) PRL_HIP_CHECK(hipEventRecord(ev_start, stream));
+    const hipStream_t stream = c.stream;
+    const int n_pages = L.n_pages;
+    if (L.ev_start) PRL_HIP_CHECK(hipEventRecord(L.ev_start, stream));
     int st;
-    if (exact) {
+    if (c.exact) {
         // (Wolf-Jolion: the inline interval test needs k / devianceMax with its bound, which the side stream is still working out)
-        if (before_refine) PRL_HIP_CHECK(hipStreamWaitEvent(stream, before_refine, 0));
-        st = launch_sweep_exact<METHOD>(sh, stream, src, dst, fp, g, cnt, wl, acc, done);
+        if (L.before_refine) PRL_HIP_CHECK(hipStreamWaitEvent(stream, L.before_refine, 0));
+        st = launch_sweep_exact<METHOD>(L, c, fp);
     } else {
-        st = launch_sweep<METHOD>(sh, stream, src, dst, fp, g, rl, cand, cnt);
+        st = launch_sweep<METHOD>(L, c, fp, stream);
     }
     if (st != PRL_OK) return st;
-    if (ev_stop) PRL_HIP_CHECK(hipEventRecord(ev_stop, stream));
-    if (before_refine) PRL_HIP_CHECK(hipStreamWaitEvent(stream, before_refine, 0));   // (Wolf-Jolion: the literal k / devianceMax of the side stream)
+    if (L.ev_stop) PRL_HIP_CHECK(hipEventRecord(L.ev_stop, stream));
+    if (L.before_refine) PRL_HIP_CHECK(hipStreamWaitEvent(stream, L.before_refine, 0));   // (Wolf-Jolion: the literal k / devianceMax of the side stream)
     // (float pipeline: a wavefront per queued pixel, a few microseconds each; big batches queue ~10^4 of them: 4096 wavefronts
     // instead of 1024 took k_refine from 0.14 to 0.05 ms on 256 A4 pages (Niblack w=31); small calls keep the cheaper launch)
     const unsigned refine_blocks = fp.flt ? (fp.total_waves > 20000u ? 1024u : 256u) : 64u;
-    hipLaunchKernelGGL((k_refine<METHOD>), dim3(refine_blocks), dim3(256), 0, stream, src, dst, fp, g, rl, wl, cnt, acc, done);
+    hipLaunchKernelGGL((k_refine<METHOD>), dim3(refine_blocks), dim3(256), 0, stream, c.src, c.dst, fp, c.d_globals, L.rl, L.wl, L.cnt, L.acc, L.done);
     PRL_HIP_CHECK(hipGetLastError());
     // From kPageMajorMin queued pixels on the corner sums are built page by page (k_group_items + k_corner_rows, which return at
     // once otherwise); calls of a few pages skip the two launches (a near-empty launch costs ~5 us, a single-page call 33).
@@ -2244,29 +2291,29 @@ int launch_fused(int sh, hipStream_t stream, const PageSet& src, const PageSetOu
     if (METHOD == PRL_WOLFJOLION) {
         // the literal devianceMax of the pages whose pixels reached the fix-up list (none, as a rule: immediate returns)
         if (page_major) {
-            hipLaunchKernelGGL(k_group_items, dim3(1), dim3(1024), 0, stream, cand, cnt, 2, g, n_pages, fp.tp.width, fp.wl_cap, ga);
+            hipLaunchKernelGGL(k_group_items, dim3(1), dim3(1024), 0, stream, L.cand, L.cnt, 2, c.d_globals, n_pages, fp.tp.width, fp.wl_cap, L.ga);
             if (rows_wide)
-                hipLaunchKernelGGL((k_corner_rows<false, 128>), rows_grid, rows_block, rows_lds, stream, src, fp, cand, ga, cnt, cacc, dst, g,
+                hipLaunchKernelGGL((k_corner_rows<false, 128>), rows_grid, rows_block, rows_lds, stream, c.src, fp, L.cand, L.ga, L.cnt, L.cacc, c.dst, c.d_globals,
                                    static_cast<unsigned*>(nullptr));
             else
-                hipLaunchKernelGGL((k_corner_rows<false, 64>), rows_grid, rows_block, rows_lds, stream, src, fp, cand, ga, cnt, cacc, dst, g,
+                hipLaunchKernelGGL((k_corner_rows<false, 64>), rows_grid, rows_block, rows_lds, stream, c.src, fp, L.cand, L.ga, L.cnt, L.cacc, c.dst, c.d_globals,
                                    static_cast<unsigned*>(nullptr));
         }
-        hipLaunchKernelGGL(k_corner_partial<false>, dim3(kSplit, 128), dim3(256), 0, stream, src, fp, cand, cnt, 2, cacc, dst, g,
+        hipLaunchKernelGGL(k_corner_partial<false>, dim3(kSplit, 128), dim3(256), 0, stream, c.src, fp, L.cand, L.cnt, 2, L.cacc, c.dst, c.d_globals,
                            static_cast<unsigned*>(nullptr));
-        hipLaunchKernelGGL(k_wolf_final, dim3(16), dim3(256), 0, stream, fp, g, cand, cacc, cnt);
-        hipLaunchKernelGGL(k_wolf_literal_coeff, dim3((n_pages + 63) / 64), dim3(64), 0, stream, fp, g, n_pages, cnt);
+        hipLaunchKernelGGL(k_wolf_final, dim3(16), dim3(256), 0, stream, fp, c.d_globals, L.cand, L.cacc, L.cnt);
+        hipLaunchKernelGGL(k_wolf_literal_coeff, dim3((n_pages + 63) / 64), dim3(64), 0, stream, fp, c.d_globals, n_pages, L.cnt);
         PRL_HIP_CHECK(hipGetLastError());
     }
     // literal fix-up of what k_refine queued: the kernel reads the queue length on the device and does nothing when it is
     // empty (the usual case), so no host round trip decides whether it runs; k_refine zeroed the accumulators it uses; the
     // workgroup that delivers a pixel's last partial sum evaluates the pixel (no separate k_fixup_final launch)
     if (page_major) {
-        hipLaunchKernelGGL(k_group_items, dim3(1), dim3(1024), 0, stream, wl, cnt, 1, g, n_pages, fp.tp.width, fp.wl_cap, ga);
-        if (rows_wide) hipLaunchKernelGGL((k_corner_rows<true, 128>), rows_grid, rows_block, rows_lds, stream, src, fp, wl, ga, cnt, acc, dst, g, done);
-        else hipLaunchKernelGGL((k_corner_rows<true, 64>), rows_grid, rows_block, rows_lds, stream, src, fp, wl, ga, cnt, acc, dst, g, done);
+        hipLaunchKernelGGL(k_group_items, dim3(1), dim3(1024), 0, stream, L.wl, L.cnt, 1, c.d_globals, n_pages, fp.tp.width, fp.wl_cap, L.ga);
+        if (rows_wide) hipLaunchKernelGGL((k_corner_rows<true, 128>), rows_grid, rows_block, rows_lds, stream, c.src, fp, L.wl, L.ga, L.cnt, L.acc, c.dst, c.d_globals, L.done);
+        else hipLaunchKernelGGL((k_corner_rows<true, 64>), rows_grid, rows_block, rows_lds, stream, c.src, fp, L.wl, L.ga, L.cnt, L.acc, c.dst, c.d_globals, L.done);
     }
-    hipLaunchKernelGGL(k_corner_partial<true>, dim3(kSplit, 16), dim3(256), 0, stream, src, fp, wl, cnt, 1, acc, dst, g, done);  // (1024 workgroups: an empty queue is the rule, and its launch should cost little)
+    hipLaunchKernelGGL(k_corner_partial<true>, dim3(kSplit, 16), dim3(256), 0, stream, c.src, fp, L.wl, L.cnt, 1, L.acc, c.dst, c.d_globals, L.done);  // (1024 workgroups: an empty queue is the rule, and its launch should cost little)
     PRL_HIP_CHECK(hipGetLastError());
     return PRL_OK;
 }
@@ -2355,18 +2402,7 @@ extern "C" int prl_hip_internal_fused_bounds(const prl_binarize_params* p, int w
     prl_binarize_geometry g;
     int st = prl_hip_binarize_geometry(p, width, height, &g);
     if (st != PRL_OK) return st;
-    ThrParams tp{};
-    tp.method = p->method;
-    tp.w = g.w;
-    tp.pw = g.padded_w;
-    tp.ph = g.padded_h;
-    tp.f = 1.0 / (double)(g.w * g.w);
-    tp.k = p->k;
-    tp.a = p->k * (1.0 / 128.0);
-    tp.b = 1.0 - p->k;
-    tp.c1 = 1.0 - p->feng_alpha1;
-    tp.k2 = p->feng_k2;
-    const FusedBounds b = fused_bounds(tp);
+    const FusedBounds b = fused_bounds(make_thr_params(p, g, width, height));
     out8[0] = b.Em; out8[1] = b.Eq; out8[2] = b.vthr; out8[3] = b.E1;
     out8[4] = b.Elit; out8[5] = b.eps1; out8[6] = b.kappa; out8[7] = 0;
     return PRL_OK;
@@ -2460,12 +2496,8 @@ extern "C" int prl_hip_internal_flt_q_error(int w, double* delta_qmin_cq)
 
 size_t fused_small_bytes(int n_pages)
 {
-    // [counters][refine list: kRefBuckets x kRefBucketCap][fix-up list][Wolf candidate list][corner sums][Wolf per-wavefront maxima][arrival counters]
-    // [... arrival counters][corner sums of Wolf-Jolion's candidates]
-    // [... corner sums of Wolf-Jolion's candidates][k_group_items: item indices by page, page starts / cursors / list]
-    return kFusedCounterBytes + sizeof(RefItem) * (size_t)kRefineCap + 2 * sizeof(WorkItem) * (size_t)kWorkCap +
-           sizeof(CornerAcc) * (size_t)kWorkCap + sizeof(float) * kSegmaxCap + sizeof(unsigned) * (size_t)kWorkCap +
-           sizeof(CornerAcc) * (size_t)kWorkCap + sizeof(unsigned) * ((size_t)kWorkCap + 3 * (size_t)std::max(n_pages, 1) + 4);
+    FusedLaunch L;
+    return work_area(nullptr, n_pages, &L);
 }
 
 // Strips of a row: uo output columns each, fetched with w - 1 halo columns; uo = 512 - (w - 1) rounded down to a multiple of 8,
@@ -2530,21 +2562,19 @@ int fused_max_pages(const ThrParams& tp)
     return (int)std::max<long long>(1, (long long)env_knobs().segmax_cap / (n_strips * n_segs));
 }
 
-// The whole pipeline of one call: threshold sweep, k_refine, literal fix-up (the last two find their queues on the device).
-int fused_run(const ThrParams& tp, const PageSet& src, int n_pages, const PageSetOut& dst, void* small,
-              PageGlobals* d_globals, hipStream_t stream, hipEvent_t ev_start, hipEvent_t ev_stop, bool bit_out,
-              bool counters_zeroed, PageGlobals* host_globals, const WolfSide* wolf_side, bool exact)
+// (a) Float-loop eligibility and the strips of a row.  `cq`: how loose the float32 pipeline's Q~ is (1 on the integer loop).
+static void plan_strips(const FusedCall& c, FusedParams& fp, double* cq)
 {
-    FusedParams fp{};
-    fp.tp = tp;
-    fp.bit_out = bit_out ? 1 : 0;
-    // non-temporal mask stores: the output stream is never re-read, and keeping it out of L2 leaves the cache to the
-    // window rows that ARE re-read (the leaving row, the compared-pixel row): 4.31-4.47 -> 4.15 ms on 256 x 4K pages
-    fp.nt_store = env_knobs().nt_store ? 1 : 0;
-    double cq = 1.0, dq = 0.0;
-    fp.flt = !exact && flt_usable(tp, src.step, &cq, &dq) ? 1 : 0;   // (exact: the integer loop for every strip - exact sums)
+    double dq = 0.0;
+    *cq = 1.0;
+    fp.flt = !c.exact && flt_usable(c.tp, c.src.step, cq, &dq) ? 1 : 0;   // (exact: the integer loop for every strip - exact sums)
     fp.flt_dq = fp.flt ? dq : 0.0;
-    fp.n_strips = strip_layout(tp, fp.flt != 0, bit_out, &fp.uo, &fp.ext);
+    fp.n_strips = strip_layout(c.tp, fp.flt != 0, c.bit_out, &fp.uo, &fp.ext);
+}
+
+// (b) The row segments of a call: fp.tier[], n_tiers, total_waves, xcd_waves.
+static int plan_segments(const ThrParams& tp, int n_pages, FusedParams& fp)
+{
     // Row segments.  Long segments amortise the (w-1)-row warm-up, short ones fill the chip and keep the tail short when it
     // drains; workgroups start in index order, so the segments come in TIERS of decreasing length (guided scheduling): each tier
     // takes about half of the rows that are left, in segments sized for ~two rounds of the chip's wavefront slots, down to a
@@ -2627,6 +2657,14 @@ int fused_run(const ThrParams& tp, const PageSet& src, int n_pages, const PageSe
         fp.total_waves = (unsigned)tw;
         fp.xcd_waves = (unsigned)xw;
     }
+    return PRL_OK;
+}
+
+// (c) The decision constants of the threshold sweep (DESIGN.md "Decision margins").
+static int decision_constants(const FusedCall& c, double cq, FusedParams& fp)
+{
+    const ThrParams& tp = c.tp;
+    const int n_pages = c.n_pages;
     fp.lane_off = (tp.w - 1) / 8;
     const FusedBounds b = fused_bounds(tp, fp.flt ? cq : 1.0);  // margins of the threshold sweep
     const FusedBounds b1 = fused_bounds(tp);                    // integer-pipeline margins (Wolf-Jolion's sweep B, literal noise terms)
@@ -2681,119 +2719,128 @@ int fused_run(const ThrParams& tp, const PageSet& src, int n_pages, const PageSe
     fp.ev2 = (float)(2.0 * b1.Ev * 1.01 / (f * f));  // in K units
     {
         double dqa = 0.0;
-        fp.flt_a = (tp.method == PRL_WOLFJOLION && !fp.flt && flt_a_usable(tp, src.step, &dqa)) ? 1 : 0;
+        fp.flt_a = (tp.method == PRL_WOLFJOLION && !fp.flt && flt_a_usable(tp, c.src.step, &dqa)) ? 1 : 0;
         // |K~ - K| <= w^2 |Q~ - Q| (+ the relative part, rho: S^2 and the fma round as in the integer pipeline's conversion)
         fp.kabs = fp.flt_a ? (float)((double)(tp.w * tp.w) * dqa * 1.01) : 0.0f;
     }
+    return PRL_OK;
+}
 
-    // [1] fix-up-list length, [2] Wolf candidate-list length, [5] pages of the page-major corner kernel, [60] epilogue arrivals;
-    // words 64 ...: the refine queue's bucket counters (kRefCounterStride apart)
-    auto* cnt = static_cast<unsigned*>(small);
-    if (host_globals) {
-        fp.ep_host = host_globals;
-        fp.ep_dev = d_globals;
-        fp.ep_counters = cnt;
-        fp.ep_pages = n_pages;
+// (e) Wolf-Jolion's schedule.
+static int wolf_schedule(const FusedCall& c, const FusedParams& fp, FusedLaunch& L)
+{
+    const ThrParams& tp = c.tp;
+    const hipStream_t stream = c.stream;
+    const WolfSide* wolf_side = c.wolf_side;
+    const int n_pages = c.n_pages;
+    // devianceMax first (binarizeWolfJolion.cpp:118-121): sweep A finds the float32 variance maximum,
+    // sweep B revisits only the wavefront segments that can hold the literal maximum and queues their
+    // candidate pixels, k_wolf_exact evaluates those literally, k_wolf_coeff forms k / devianceMax.
+    if (fp.total_waves > env_knobs().segmax_cap) {  // (unreachable through the C ABI: its page chunks follow fused_max_pages)
+        set_error_detail("Wolf-Jolion: more wavefronts in one call than per-wavefront maxima slots");
+        return PRL_ERR_BAD_ARG;
     }
-    auto* rl = reinterpret_cast<RefItem*>(static_cast<uint8_t*>(small) + kFusedCounterBytes);
-    auto* wl = reinterpret_cast<WorkItem*>(static_cast<uint8_t*>(small) + kFusedCounterBytes + sizeof(RefItem) * (size_t)kRefineCap);
-    auto* cand = wl + kWorkCap;
-    auto* acc = reinterpret_cast<CornerAcc*>(cand + kWorkCap);
-    fp.segmax = reinterpret_cast<float*>(acc + kWorkCap);
-    auto* cacc = reinterpret_cast<CornerAcc*>(reinterpret_cast<unsigned*>(fp.segmax + kSegmaxCap) + kWorkCap);   // (behind the arrival counters)
-    GroupArrays ga;
-    ga.sidx = reinterpret_cast<unsigned*>(cacc + kWorkCap);
-    ga.pstart = ga.sidx + kWorkCap;
-    ga.pcur = ga.pstart + n_pages + 1;
-    ga.plist = ga.pcur + n_pages;
-    if (!counters_zeroed) PRL_HIP_CHECK(hipMemsetAsync(cnt, 0, kFusedCounterBytes, stream));
+    // (cv::minMaxLoc(imageInput) rides on sweep A - every window row a wavefront fetches goes into a running
+    // minimum - plus a small kernel for the bottom rows / right columns the sweeps never fetch; Feng, which has no
+    // sweep, uses k_page_min)
+    // Schedule (round 4).  On the caller's stream: sweep A (float32 variance maximum per page and per wavefront), the
+    // threshold sweep - its coefficient comes from sweep A's maximum with a margin for the difference (k_fused) -, k_refine
+    // and the fix-up.  On the workspace's side stream, beside the two sweeps: the page minimum of the border bands, sweep B
+    // (revisits the wavefronts that can hold the maximum: EXACT integer maximum of K, and the candidate pixels) and
+    // k_wolf_interval (k / devianceMax with a bound of a few 10^-9 on its distance from the literal one), for which
+    // k_refine waits.  The literal devianceMax itself - absolute integral corners of every candidate, the part that cost
+    // 0.2-13 ms - is only computed when a pixel reaches the literal fix-up, and then for that page only (k_corner_partial
+    // <false>, k_wolf_final, k_wolf_literal_coeff: they return at once otherwise).  256 A4 pages at the header defaults:
+    // profiles/r04/wolf_schedule_ab.txt.  Without a side stream (PRL_HIP_WOLF_SIDE=0, hooks build): the same kernels in
+    // order on one stream.
+    hipStream_t ss = wolf_side ? wolf_side->stream : stream;
+    auto border_min = [&](hipStream_t q) -> int {
+        const int band = std::min(std::max(tp.w + 8, 16), std::max(tp.width, tp.height));
+        for (int first = 0; first < n_pages; first += 32768) {  // grid.y limit
+            hipLaunchKernelGGL(k_page_min_border, dim3(16, std::min(32768, n_pages - first)), dim3(256), 0, q, pages_from(c.src, first),
+                               tp.width, tp.height, band, c.d_globals + first);
+        }
+        PRL_HIP_CHECK(hipGetLastError());
+        return PRL_OK;
+    };
+    // Between the fork and the join the side stream reads the caller's pages: an error return in that span first waits
+    // for it (the API must not hand an error back while its kernels still run on the caller's memory).
+    auto forked = [&]() -> int {
+        int st;
+        if (wolf_side) {
+            PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_fork, stream));          // (globals and counters are initialised)
+            PRL_HIP_CHECK(hipStreamWaitEvent(ss, wolf_side->ev_fork, 0));
+        }
+        PRL_HIP_CHECK(hipMemsetAsync(L.cacc, 0, sizeof(CornerAcc) * (size_t)kWorkCap, ss));   // (only the lazy literal path uses it)
+        st = border_min(ss);
+        if (st != PRL_OK) return st;
+        if (wolf_side) PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_min, ss));
+        st = launch_sweep<kWolfMax>(L, c, fp, stream);
+        if (st != PRL_OK) return st;
+        if (wolf_side) {
+            PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_a, stream));
+            PRL_HIP_CHECK(hipStreamWaitEvent(ss, wolf_side->ev_a, 0));
+        }
+        st = launch_sweep<kWolfCollect>(L, c, fp, ss);
+        if (st != PRL_OK) return st;
+        hipLaunchKernelGGL(k_wolf_interval, dim3((n_pages + 63) / 64), dim3(64), 0, ss, fp, c.d_globals, n_pages);
+        PRL_HIP_CHECK(hipGetLastError());
+        if (env_knobs().debug) {
+            unsigned hc[4] = {0, 0, 0, 0};
+            (void)hipMemcpyAsync(hc, L.cnt, sizeof(hc), hipMemcpyDeviceToHost, ss);
+            (void)hipStreamSynchronize(ss);
+            std::fprintf(stderr, "[prl_hip] Wolf-Jolion: %u maximum-deviation candidates on %d pages (cap %u)\n", hc[2], n_pages, fp.wl_cap);
+        }
+        if (wolf_side) {
+            PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_coeff, ss));
+            PRL_HIP_CHECK(hipStreamWaitEvent(stream, wolf_side->ev_min, 0));   // the threshold sweep needs the whole page minimum
+            L.before_refine = wolf_side->ev_coeff;
+        }
+        return launch_fused<PRL_WOLFJOLION>(L, c, fp);
+    };
+    const int st = forked();
+    if (st != PRL_OK && wolf_side) (void)hipStreamSynchronize(wolf_side->stream);
+    return st;
+}
+
+// The whole pipeline of one call: threshold sweep, k_refine, literal fix-up (the last two find their queues on the device).
+int fused_run(const FusedCall& c)
+{
+    const ThrParams& tp = c.tp;
+    FusedParams fp{};
+    fp.tp = tp;
+    fp.bit_out = c.bit_out ? 1 : 0;
+    // non-temporal mask stores: the output stream is never re-read, and keeping it out of L2 leaves the cache to the
+    // window rows that ARE re-read (the leaving row, the compared-pixel row): 4.31-4.47 -> 4.15 ms on 256 x 4K pages
+    fp.nt_store = env_knobs().nt_store ? 1 : 0;
+    double cq;
+    plan_strips(c, fp, &cq);
+    int st = plan_segments(tp, c.n_pages, fp);
+    if (st != PRL_OK) return st;
+    st = decision_constants(c, cq, fp);
+    if (st != PRL_OK) return st;
+
+    FusedLaunch L;
+    work_area(static_cast<uint8_t*>(c.small), c.n_pages, &L);   // (d)
+    L.ev_start = c.ev_start;
+    L.ev_stop = c.ev_stop;
+    L.sh = (tp.w - 1) & 7;
+    L.n_pages = c.n_pages;
+    fp.segmax = L.segmax;
+    if (c.host_globals) {
+        fp.ep_host = c.host_globals;
+        fp.ep_dev = c.d_globals;
+        fp.ep_counters = L.cnt;
+        fp.ep_pages = c.n_pages;
+    }
+    if (!c.counters_zeroed) PRL_HIP_CHECK(hipMemsetAsync(L.cnt, 0, kFusedCounterBytes, c.stream));
 
     if (tp.method == PRL_FENG) {
-        int st = page_min_run(tp, src, n_pages, d_globals, stream);
+        st = page_min_run(tp, c.src, c.n_pages, c.d_globals, c.stream);
         if (st != PRL_OK) return st;
     }
-    const int sh = (tp.w - 1) & 7;
-    if (tp.method == PRL_WOLFJOLION) {
-        // devianceMax first (binarizeWolfJolion.cpp:118-121): sweep A finds the float32 variance maximum,
-        // sweep B revisits only the wavefront segments that can hold the literal maximum and queues their
-        // candidate pixels, k_wolf_exact evaluates those literally, k_wolf_coeff forms k / devianceMax.
-        if (fp.total_waves > env_knobs().segmax_cap) {  // (unreachable through the C ABI: its page chunks follow fused_max_pages)
-            set_error_detail("Wolf-Jolion: more wavefronts in one call than per-wavefront maxima slots");
-            return PRL_ERR_BAD_ARG;
-        }
-        // (cv::minMaxLoc(imageInput) rides on sweep A - every window row a wavefront fetches goes into a running
-        // minimum - plus a small kernel for the bottom rows / right columns the sweeps never fetch; Feng, which has no
-        // sweep, uses k_page_min)
-        // Schedule (round 4).  On the caller's stream: sweep A (float32 variance maximum per page and per wavefront), the
-        // threshold sweep - its coefficient comes from sweep A's maximum with a margin for the difference (k_fused) -, k_refine
-        // and the fix-up.  On the workspace's side stream, beside the two sweeps: the page minimum of the border bands, sweep B
-        // (revisits the wavefronts that can hold the maximum: EXACT integer maximum of K, and the candidate pixels) and
-        // k_wolf_interval (k / devianceMax with a bound of a few 10^-9 on its distance from the literal one), for which
-        // k_refine waits.  The literal devianceMax itself - absolute integral corners of every candidate, the part that cost
-        // 0.2-13 ms - is only computed when a pixel reaches the literal fix-up, and then for that page only (k_corner_partial
-        // <false>, k_wolf_final, k_wolf_literal_coeff: they return at once otherwise).  256 A4 pages at the header defaults:
-        // profiles/r04/wolf_schedule_ab.txt.  Without a side stream (PRL_HIP_WOLF_SIDE=0, hooks build): the same kernels in
-        // order on one stream.
-        hipStream_t ss = wolf_side ? wolf_side->stream : stream;
-        auto border_min = [&](hipStream_t q) -> int {
-            const int band = std::min(std::max(tp.w + 8, 16), std::max(tp.width, tp.height));
-            for (int first = 0; first < n_pages; first += 32768) {  // grid.y limit
-                PageSet part = src;
-                if (part.table) part.table += first; else part.base += (size_t)first * part.page_stride;
-                hipLaunchKernelGGL(k_page_min_border, dim3(16, std::min(32768, n_pages - first)), dim3(256), 0, q, part,
-                                   tp.width, tp.height, band, d_globals + first);
-            }
-            PRL_HIP_CHECK(hipGetLastError());
-            return PRL_OK;
-        };
-        // Between the fork and the join the side stream reads the caller's pages: an error return in that span first waits
-        // for it (the API must not hand an error back while its kernels still run on the caller's memory).
-        auto forked = [&]() -> int {
-            int st;
-            if (wolf_side) {
-                PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_fork, stream));          // (globals and counters are initialised)
-                PRL_HIP_CHECK(hipStreamWaitEvent(ss, wolf_side->ev_fork, 0));
-            }
-            PRL_HIP_CHECK(hipMemsetAsync(cacc, 0, sizeof(CornerAcc) * (size_t)kWorkCap, ss));   // (only the lazy literal path uses it)
-            st = border_min(ss);
-            if (st != PRL_OK) return st;
-            if (wolf_side) PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_min, ss));
-            st = launch_sweep<kWolfMax>(sh, stream, src, dst, fp, d_globals, rl, cand, cnt);
-            if (st != PRL_OK) return st;
-            if (wolf_side) {
-                PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_a, stream));
-                PRL_HIP_CHECK(hipStreamWaitEvent(ss, wolf_side->ev_a, 0));
-            }
-            st = launch_sweep<kWolfCollect>(sh, ss, src, dst, fp, d_globals, rl, cand, cnt);
-            if (st != PRL_OK) return st;
-            hipLaunchKernelGGL(k_wolf_interval, dim3((n_pages + 63) / 64), dim3(64), 0, ss, fp, d_globals, n_pages);
-            PRL_HIP_CHECK(hipGetLastError());
-            if (env_knobs().debug) {
-                unsigned hc[4] = {0, 0, 0, 0};
-                (void)hipMemcpyAsync(hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, ss);
-                (void)hipStreamSynchronize(ss);
-                std::fprintf(stderr, "[prl_hip] Wolf-Jolion: %u maximum-deviation candidates on %d pages (cap %u)\n", hc[2], n_pages, fp.wl_cap);
-            }
-            hipEvent_t before_refine = nullptr;
-            if (wolf_side) {
-                PRL_HIP_CHECK(hipEventRecord(wolf_side->ev_coeff, ss));
-                PRL_HIP_CHECK(hipStreamWaitEvent(stream, wolf_side->ev_min, 0));   // the threshold sweep needs the whole page minimum
-                before_refine = wolf_side->ev_coeff;
-            }
-            return launch_fused<PRL_WOLFJOLION>(sh, stream, src, dst, fp, d_globals, rl, wl, cand, acc, cnt, ev_start, ev_stop, n_pages, ga,
-                                                before_refine, cacc, exact);
-        };
-        const int st = forked();
-        if (st != PRL_OK && wolf_side) (void)hipStreamSynchronize(wolf_side->stream);
-        return st;
-    }
-    switch (tp.method) {
-    case PRL_SAUVOLA: return launch_fused<PRL_SAUVOLA>(sh, stream, src, dst, fp, d_globals, rl, wl, cand, acc, cnt, ev_start, ev_stop, n_pages, ga, nullptr, nullptr, exact);
-    case PRL_NIBLACK: return launch_fused<PRL_NIBLACK>(sh, stream, src, dst, fp, d_globals, rl, wl, cand, acc, cnt, ev_start, ev_stop, n_pages, ga, nullptr, nullptr, exact);
-    case PRL_NICK: return launch_fused<PRL_NICK>(sh, stream, src, dst, fp, d_globals, rl, wl, cand, acc, cnt, ev_start, ev_stop, n_pages, ga, nullptr, nullptr, exact);
-    case PRL_FENG: return launch_fused<PRL_FENG>(sh, stream, src, dst, fp, d_globals, rl, wl, cand, acc, cnt, ev_start, ev_stop, n_pages, ga, nullptr, nullptr, exact);
-    default: return PRL_ERR_BAD_ARG;
-    }
+    if (tp.method == PRL_WOLFJOLION) return wolf_schedule(c, fp, L);
+    return with_method(tp.method, [&](auto m) { return launch_fused<m.value>(L, c, fp); });
 }
 
 }  // namespace prl_hip

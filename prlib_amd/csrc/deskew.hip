@@ -1241,15 +1241,13 @@ int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const uint8_t* 
     std::vector<int> h_thr((size_t)sub);
     for (int first = 0; first < n_pages; first += sub) {
         const int cnt = std::min(sub, n_pages - first);
-        PageSet g{};
+        PageSet g = pages_from(page_set(src, src_page_stride, src_step), first);
         if (channels != 1) {
             uint8_t* gray_ws = static_cast<uint8_t*>(ctx->ppht_buf[2]);
             st = prl_hip_bgr2gray_batch_device(cnt, channels, src + (size_t)first * src_page_stride, src_page_stride, src_step, width, height,
                                                gray_ws, gray_page, (size_t)width, hs);
             if (st != PRL_OK) return st;
-            g.base = gray_ws; g.page_stride = gray_page; g.step = (size_t)width;
-        } else {
-            g.base = src + (size_t)first * src_page_stride; g.page_stride = src_page_stride; g.step = src_step;
+            g = page_set(gray_ws, gray_page, (size_t)width);
         }
         PRL_HIP_CHECK(hipMemsetAsync(d_hist, 0, (size_t)cnt * 256 * 4, hs));
         const dim3 hg((unsigned)std::min(4, (width + 1023) / 1024), (unsigned)std::min(height, 64), (unsigned)cnt);
@@ -1275,7 +1273,7 @@ int deskew_find(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_
     const size_t gray_page = r256((size_t)width * height);
     std::lock_guard<std::mutex> lk(ctx->ppht_mu);
     int st;
-    PageSet g{};
+    PageSet g = page_set(src, src_page_stride, src_step);
     if (channels != 1) {  // deskew.cpp:214-217
         st = ensure_buffer(&ctx->ppht_buf[2], &ctx->ppht_bytes[2], gray_page * (size_t)cnt);
         if (st != PRL_OK) return st;
@@ -1283,9 +1281,7 @@ int deskew_find(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_
         st = prl_hip_bgr2gray_batch_device(cnt, channels, src, src_page_stride, src_step, width, height, gray_ws, gray_page,
                                            (size_t)width, hs);
         if (st != PRL_OK) return st;
-        g.base = gray_ws; g.page_stride = gray_page; g.step = (size_t)width;
-    } else {
-        g.base = src; g.page_stride = src_page_stride; g.step = src_step;
+        g = page_set(gray_ws, gray_page, (size_t)width);
     }
     std::vector<std::vector<int>> lines;
     // cv::threshold(..., THRESH_BINARY | THRESH_OTSU) (:224) + findAngle's bitwise_not (:146): points = (p <= otsu)
@@ -1324,10 +1320,8 @@ int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, 
     ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
     PRL_HIP_CHECK(hipMemcpyAsync(ctx->small, plan.warp.data(), plan.warp.size(), hipMemcpyHostToDevice, hs));
     PRL_HIP_CHECK(hipStreamSynchronize(hs));  // pageable source
-    PageSet s{};
-    s.base = src; s.page_stride = src_page_stride; s.step = src_step;
-    PageSetOut d{};
-    d.base = dst; d.page_stride = dst_page_stride; d.step = dst_step;
+    const PageSet s = page_set(src, src_page_stride, src_step);
+    const PageSetOut d = page_set_out(dst, dst_page_stride, dst_step);
     return launch_warp(channels, s, d, width, height, cnt, plan.max_ow, plan.max_oh, static_cast<const WarpPage*>(ctx->small), hs);
 }
 
@@ -1432,10 +1426,8 @@ int prl_hip_rotate_batch_device(int n_pages, int channels, const double* angles,
         }
         PRL_HIP_CHECK(hipMemcpyAsync(ctx->small, wp.data(), sizeof(WarpPage) * (size_t)cnt, hipMemcpyHostToDevice, hs));
         PRL_HIP_CHECK(hipStreamSynchronize(hs));  // `wp` is pageable host memory reused by the next chunk
-        PageSet s{};
-        s.base = d_src + (size_t)first * src_page_stride; s.page_stride = src_page_stride; s.step = src_step;
-        PageSetOut d{};
-        d.base = d_dst + (size_t)first * dst_page_stride; d.page_stride = dst_page_stride; d.step = dst_step;
+        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
+        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
         st = launch_warp(channels, s, d, width, height, cnt, max_ow, max_oh, static_cast<const WarpPage*>(ctx->small), hs);
         if (st != PRL_OK) return st;
     }
@@ -1465,8 +1457,7 @@ int prl_hip_houghp_device(const uint8_t* d_image, size_t step, int width, int he
     StageRelease release{ctx, hs};
     st = prl_hip_invert_batch_device(1, d_image, 0, step, width, height, static_cast<uint8_t*>(ctx->stage), bytes, (size_t)width, stream);
     if (st != PRL_OK) return st;
-    PageSet g{};
-    g.base = static_cast<uint8_t*>(ctx->stage); g.page_stride = 0; g.step = (size_t)width;
+    const PageSet g = page_set(static_cast<uint8_t*>(ctx->stage), 0, (size_t)width);
     std::vector<std::vector<int>> out;
     {
         std::lock_guard<std::mutex> lk(ctx->ppht_mu);
@@ -1513,8 +1504,7 @@ int prl_hip_find_angle_batch_device(int n_pages, const uint8_t* d_image, size_t 
     const int chunk = deskew_pages_per_pass(n_pages, width, height);
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
-        PageSet g{};
-        g.base = d_image + (size_t)first * page_stride; g.page_stride = page_stride; g.step = step;
+        const PageSet g = pages_from(page_set(d_image, page_stride, step), first);
         std::vector<std::vector<int>> lines;
         {
             std::lock_guard<std::mutex> lk(ctx->ppht_mu);

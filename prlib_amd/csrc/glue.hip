@@ -142,8 +142,8 @@ int common_args(int n_pages, const uint8_t* d_src, size_t sps, size_t sstep, siz
     if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
     if (n_pages < 0 || !d_src || !d_dst || sstep < src_row_bytes || dstep < dst_row_bytes) return PRL_ERR_BAD_ARG;
     if (height > 65535) return PRL_ERR_BAD_ARG;  // grid.y limit (one grid row per image row)
-    a->ps.base = d_src; a->ps.page_stride = sps; a->ps.step = sstep;
-    a->pd.base = d_dst; a->pd.page_stride = dps; a->pd.step = dstep;
+    a->ps = page_set(d_src, sps, sstep);
+    a->pd = page_set_out(d_dst, dps, dstep);
     a->grid = dim3((unsigned)((width + 1023) / 1024), (unsigned)height, (unsigned)n_pages);  // 4 px per thread
     return PRL_OK;
 }

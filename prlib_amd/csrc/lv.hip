@@ -377,10 +377,8 @@ int prl_hip_binarize_lv_batch_device(int n_pages, int with_filters, double coeff
     LvParams p{width, height, with_filters ? 1 : 0, min_result_variance, coeff, gamma};
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
-        PageSet s{};
-        s.base = d_src + (size_t)first * src_page_stride; s.page_stride = src_page_stride; s.step = src_step;
-        PageSetOut d{};
-        d.base = d_dst + (size_t)first * dst_page_stride; d.page_stride = dst_page_stride; d.step = dst_step;
+        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
+        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
         const dim3 grid((unsigned)((width + FX - 1) / FX), (unsigned)((height + FY - 1) / FY), (unsigned)cnt);    // k_lv_final
         const dim3 mgrid((unsigned)((width + MX - 1) / MX), (unsigned)((height + MY - 1) / MY), (unsigned)cnt);   // variance passes
         hipLaunchKernelGGL(k_lv_init, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, hs, d_stats, cnt);

@@ -357,12 +357,8 @@ int median_run(const MedGeom& g, size_t times, const PageSet& src, const PageSet
 {
     const int R = g.W * g.C;
     if (g.k == 1 || times == 0) return in_place ? PRL_OK : median_copy(src, dst, R, g.H, n, stream);
-    PageSetOut t{};
-    t.base = tmp; t.page_stride = (size_t)R * g.H; t.step = (size_t)R;
-    PageSet ts{};
-    ts.base = tmp; ts.page_stride = t.page_stride; ts.step = t.step;
-    PageSet ds{};
-    ds.base = dst.base; ds.page_stride = dst.page_stride; ds.step = dst.step;
+    const PageSetOut t = page_set_out(tmp, (size_t)R * g.H, (size_t)R);
+    const PageSet ts = as_source(t), ds = as_source(dst);
     const bool generic = env_knobs().median_generic;
     PageSet cur = src;
     int st = PRL_OK;
@@ -437,10 +433,8 @@ int prl_hip_median_batch_device(int n_pages, int channels, int ksize, size_t tim
     if (st != PRL_OK) return st;
     DeviceRelease release{ctx, hs};
     for (int first = 0; first < n_pages; first += chunk) {
-        PageSet s{};
-        s.base = d_src + (size_t)first * src_page_stride; s.page_stride = src_page_stride; s.step = src_step;
-        PageSetOut d{};
-        d.base = d_dst + (size_t)first * dst_page_stride; d.page_stride = dst_page_stride; d.step = dst_step;
+        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
+        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
         st = median_run(g, work ? times : 0, s, d, std::min(chunk, n_pages - first), in_place,
                         need_tmp ? static_cast<uint8_t*>(ctx->scratch) : nullptr, hs);
         if (st != PRL_OK) return st;

@@ -705,10 +705,7 @@ int morph_large_run(int iterations, const PageSet& src, int n_pages, int width, 
     const int n = iterations > 0 ? iterations : -iterations;
     const int per_op = (n + kMaxN - 1) / kMaxN, passes = 2 * per_op;
     const dim3 grid((width + TW - 1) / TW, (height + TH - 1) / TH, n_pages);
-    PageSetOut t{};
-    t.base = tmp;
-    t.page_stride = tmp_step * (size_t)height;
-    t.step = tmp_step;
+    const PageSetOut t = page_set_out(tmp, tmp_step * (size_t)height, tmp_step);
     PageSet cur = src;
     for (int i = 0; i < passes; ++i) {
         const bool first_op = i < per_op;

@@ -840,8 +840,7 @@ static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_
     const size_t px = (size_t)width * height;
     uint8_t* L = planes;
     uint8_t* AB = L + px * (size_t)cnt;
-    PageSet ps{};
-    ps.base = src; ps.page_stride = src_page_stride; ps.step = src_step;
+    const PageSet ps = page_set(src, src_page_stride, src_step);
     const dim3 grid((width + 255) / 256, height, cnt);
     hipLaunchKernelGGL(k_lbgr2lab, grid, dim3(256), 0, s, ps, channels, width, height, lt, L, AB, px);
     PRL_HIP_CHECK(hipGetLastError());
@@ -858,12 +857,8 @@ static int nlm_locked(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, 
     uint8_t* AB = L + px * (size_t)cnt;
     uint8_t* L2 = AB + 2 * px * (size_t)cnt;
     uint8_t* AB2 = L2 + px * (size_t)cnt;
-    PageSet sl{}, sab{};
-    sl.base = L; sl.page_stride = px; sl.step = (size_t)width;
-    sab.base = AB; sab.page_stride = 2 * px; sab.step = 2 * (size_t)width;
-    PageSetOut dl{}, dab{};
-    dl.base = L2; dl.page_stride = px; dl.step = (size_t)width;
-    dab.base = AB2; dab.page_stride = 2 * px; dab.step = 2 * (size_t)width;
+    const PageSet sl = page_set(L, px, (size_t)width), sab = page_set(AB, 2 * px, 2 * (size_t)width);
+    const PageSetOut dl = page_set_out(L2, px, (size_t)width), dab = page_set_out(AB2, 2 * px, 2 * (size_t)width);
     st = nlm_planes_locked(ctx, 0, cnt, 1, strength, sl, width, height, dl, s);
     if (st != PRL_OK) return st;
     return nlm_planes_locked(ctx, 1, cnt, 2, 3.0f, sab, width, height, dab, s);  // hForColorComponents = 3
@@ -881,8 +876,7 @@ static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8
     const size_t px = (size_t)width * height;
     const uint8_t* L2 = planes + 3 * px * (size_t)cnt;
     const uint8_t* AB2 = L2 + px * (size_t)cnt;
-    PageSetOut pd{};
-    pd.base = dst; pd.page_stride = dst_page_stride; pd.step = dst_step;
+    const PageSetOut pd = page_set_out(dst, dst_page_stride, dst_step);
     const dim3 grid((width + 255) / 256, height, cnt);
     hipLaunchKernelGGL(k_lab2lbgr, grid, dim3(256), 0, s, L2, AB2, px, channels, width, height, lt, pd);
     PRL_HIP_CHECK(hipGetLastError());
@@ -941,14 +935,8 @@ int prl_hip_nlm_planes_device(int n_pages, int channels, float h, const uint8_t*
     st = device_acquire(ctx, s);
     if (st != PRL_OK) return st;
     DeviceRelease release{ctx, s};
-    PageSet ps{};
-    ps.base = d_src;
-    ps.page_stride = src_page_stride;
-    ps.step = src_step;
-    PageSetOut pd{};
-    pd.base = d_dst;
-    pd.page_stride = dst_page_stride;
-    pd.step = dst_step;
+    const PageSet ps = page_set(d_src, src_page_stride, src_step);
+    const PageSetOut pd = page_set_out(d_dst, dst_page_stride, dst_step);
     return nlm_planes_locked(ctx, 0, n_pages, channels, h, ps, width, height, pd, s);
 }
 

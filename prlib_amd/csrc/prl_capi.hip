@@ -216,6 +216,25 @@ void ws_free(StreamWs* ws)
     ws->clean_pages = 0;
 }
 
+// Wolf-Jolion's side stream and its events, created on the first call that wants them (ws_free destroys them).  Built in a local
+// and published only when the stream and all four events exist: a half-made side would be taken for a whole one by the next
+// call (stream set, events null).
+int ws_wolf_side(StreamWs* ws)
+{
+    if (ws->wolf.stream) return PRL_OK;
+    WolfSide side{};
+    hipError_t e = hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking);
+    for (hipEvent_t* ev : {&side.ev_fork, &side.ev_min, &side.ev_a, &side.ev_coeff})
+        if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        for (hipEvent_t ev : {side.ev_fork, side.ev_min, side.ev_a, side.ev_coeff}) if (ev) (void)hipEventDestroy(ev);
+        if (side.stream) (void)hipStreamDestroy(side.stream);
+        PRL_HIP_CHECK(e);
+    }
+    ws->wolf = side;
+    return PRL_OK;
+}
+
 DeviceCtx::~DeviceCtx() = default;  // (process teardown: the driver reclaims device memory)
 
 int current_device(int* dev)
@@ -558,8 +577,9 @@ int geometry_impl(const prl_binarize_params* p, int width, int height, prl_binar
     return PRL_OK;
 }
 
-ThrParams make_thr_params(const prl_binarize_params* p, const prl_binarize_geometry& g, int width,
-                          int height)
+}  // namespace
+
+ThrParams make_thr_params(const prl_binarize_params* p, const prl_binarize_geometry& g, int width, int height)
 {
     ThrParams tp{};
     tp.method = p->method;
@@ -584,6 +604,8 @@ ThrParams make_thr_params(const prl_binarize_params* p, const prl_binarize_geome
     return tp;
 }
 
+namespace {
+
 struct SlotLayout {
     size_t table_bytes, globals_bytes, total;
 };
@@ -596,87 +618,31 @@ SlotLayout slot_layout(int n_pages)
     return l;
 }
 
-// The flagged pages of a PRL_MODE_AUTO call (a queue overflowed: pathological inputs only - more than 2^21 pixels of a call inside
-// the float32 decision band, or 2^17 within ~1e-6 of their threshold), redone by the literal pipeline (and its morphology pass)
-// from the caller's own source pages into the caller's destination pages, as ONE batch: page-pointer tables on the device,
-// chunks sized by the literal scratch budget.  (Round 3 redid them one by one - a launch sequence and a workspace check per page.)
-int redo_pages_literal(StreamWs* ws, const PendingCall& pc, const std::vector<int>& idx)
+// The morphology pass from a thresholded mask buffer into `dst`: the variant follows the buffer's form (bit plane or byte mask)
+// and the radius (large radii: chained single-operator passes through `tmp`, one more page-sized buffer per page).
+int morph_from_mask(int morph, const PageSetOut& mask, bool bit_plane, int n_pages, int width, int height, const PageSetOut& dst,
+                    uint8_t* tmp, size_t tmp_step, hipStream_t stream)
 {
-    const int n = (int)idx.size();
-    if (n == 0) return PRL_OK;
-    prl_binarize_geometry g;
-    int st = geometry_impl(&pc.params, pc.width, pc.height, &g);
-    if (st != PRL_OK) return st;
-    const ThrParams tp = make_thr_params(&pc.params, g, pc.width, pc.height);
-    const int morph = pc.params.morph_iterations;
-    const size_t lit = r256(literal_scratch_per_page(tp));
-    const size_t mask_step = ((size_t)g.out_w + 63) / 64 * 64, mask_page = r256(mask_step * (size_t)g.out_h);
-    const bool large = morph != 0 && std::abs(morph) > kMorphMaxFusedRadius;
-    const size_t per_page = lit + (morph != 0 ? mask_page * (large ? 2 : 1) : 0);
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, literal_scratch_budget() / per_page));
-    const size_t tab_bytes = r256(sizeof(void*) * (size_t)n), glob_bytes = r256(sizeof(PageGlobals) * (size_t)n);
-    // [literal integral planes x chunk][byte masks x chunk (morph != 0)][second mask buffer (large radii)][PageGlobals x n][src table][dst table]
-    st = ws_grow(&ws->scratch, &ws->scratch_bytes, per_page * (size_t)chunk + glob_bytes + 2 * tab_bytes, ws->stream);
-    if (st != PRL_OK) return st;
-    auto* base = static_cast<uint8_t*>(ws->scratch);
-    uint8_t* d_mask = base + lit * (size_t)chunk;
-    uint8_t* d_mask2 = d_mask + mask_page * (size_t)chunk;
-    uint8_t* tail = base + per_page * (size_t)chunk;
-    auto* d_g = reinterpret_cast<PageGlobals*>(tail);
-    auto** d_src_tab = reinterpret_cast<const uint8_t**>(tail + glob_bytes);
-    auto** d_dst_tab = reinterpret_cast<uint8_t**>(tail + glob_bytes + tab_bytes);
-    std::vector<const uint8_t*> h_src((size_t)n);
-    std::vector<uint8_t*> h_dst((size_t)n);
-    for (int j = 0; j < n; ++j) {
-        const size_t i = (size_t)idx[(size_t)j];
-        h_src[(size_t)j] = pc.src_tab.empty() ? pc.src.base + i * pc.src.page_stride : pc.src_tab[i];
-        h_dst[(size_t)j] = pc.dst_tab.empty() ? pc.dst.base + i * pc.dst.page_stride : pc.dst_tab[i];
-    }
-    PRL_HIP_CHECK(hipMemcpyAsync(d_src_tab, h_src.data(), sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
-    PRL_HIP_CHECK(hipMemcpyAsync(d_dst_tab, h_dst.data(), sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
-    PRL_HIP_CHECK(hipStreamSynchronize(ws->stream));   // (the host vectors go out of scope; pageable memory)
-    st = init_globals_run(d_g, n, ws->stream);
-    if (st != PRL_OK) return st;
-    for (int c0 = 0; c0 < n; c0 += chunk) {
-        const int cnt = std::min(chunk, n - c0);
-        PageSet src{};
-        src.table = d_src_tab + c0;
-        src.step = pc.src.step;
-        PageSetOut out{};
-        out.table = d_dst_tab + c0;
-        out.step = pc.dst.step;
-        if (tp.method == PRL_WOLFJOLION || tp.method == PRL_FENG) {
-            st = page_min_run(tp, src, cnt, d_g + c0, ws->stream);
-            if (st != PRL_OK) return st;
-        }
-        PageSetOut thr = out;
-        if (morph != 0) {
-            thr = PageSetOut{};
-            thr.base = d_mask;
-            thr.page_stride = mask_page;
-            thr.step = mask_step;
-        }
-        st = literal_run(tp, src, 0, cnt, thr, ws->scratch, d_g + c0, ws->stream);
-        if (st != PRL_OK) return st;
-        if (morph == 0) continue;
-        PageSet msrc{};
-        msrc.base = d_mask;
-        msrc.page_stride = mask_page;
-        msrc.step = mask_step;
-        if (!large) st = morph_binary_run(morph, msrc, cnt, g.out_w, g.out_h, out, ws->stream);
-        else st = morph_large_run(morph, msrc, cnt, g.out_w, g.out_h, out, d_mask2, mask_step, ws->stream);
-        if (st != PRL_OK) return st;
-    }
-    return PRL_OK;
+    const PageSet msrc = as_source(mask);
+    if (bit_plane) return morph_bitplane_run(morph, msrc, n_pages, width, height, dst, stream);
+    if (std::abs(morph) <= kMorphMaxFusedRadius) return morph_binary_run(morph, msrc, n_pages, width, height, dst, stream);
+    return morph_large_run(morph, msrc, n_pages, width, height, dst, tmp, tmp_step, stream);
 }
 
-// The second chance of pages whose REFINE QUEUE overflowed (bit 0 of worklist_overflow: more pixels inside the float32 decision band
-// than the queue holds - pages of stripes whose levels sit near their own threshold): the exact sweep (k_fused_exact: integer sums
-// for every strip, the float64 interval test inline, no queue) over those pages as one batch, ties through the usual fix-up, then
-// the morphology pass.  `still` receives the pages that overflowed the fix-up list on the way (true ties by the 10^5): those go to
-// the literal pipeline.  Own workspace layout inside ws->scratch; synchronises the stream (it reads the flags back).
-int redo_pages_exact(StreamWs* ws, const PendingCall& pc, const std::vector<int>& idx, std::vector<int>* still, CallStats* cs)
+// The flagged pages of a PRL_MODE_AUTO call, redone from the caller's own source pages into the caller's destination pages as ONE
+// batch (page-pointer tables on the device, the threshold step in chunks, then the morphology pass), in one of two ways:
+//  * literal (`still` == nullptr): the literal pipeline, for pages whose fix-up list overflowed (pathological inputs only - more
+//    than 2^21 pixels of a call inside the float32 decision band, or 2^17 within ~1e-6 of their threshold); chunks sized by the
+//    literal scratch budget.  (Round 3 redid them one by one - a launch sequence and a workspace check per page.)
+//  * exact: the second chance of pages whose REFINE QUEUE overflowed (bit 0 of worklist_overflow: more pixels inside the float32
+//    decision band than the queue holds - pages of stripes whose levels sit near their own threshold): the exact sweep
+//    (k_fused_exact: integer sums for every strip, the float64 interval test inline, no queue), ties through the usual fix-up.
+//    `still` receives the pages that overflowed the fix-up list on the way (true ties by the 10^5): those go to the literal
+//    pipeline.  Synchronises the stream (it reads the flags back).
+// Own workspace layout inside ws->scratch.
+int redo_pages(StreamWs* ws, const PendingCall& pc, const std::vector<int>& idx, std::vector<int>* still = nullptr, CallStats* cs = nullptr)
 {
+    const bool exact = still != nullptr;
     const int n = (int)idx.size();
     if (n == 0) return PRL_OK;
     prl_binarize_geometry g;
@@ -686,59 +652,70 @@ int redo_pages_exact(StreamWs* ws, const PendingCall& pc, const std::vector<int>
     const int morph = pc.params.morph_iterations;
     const size_t mask_step = ((size_t)g.out_w + 63) / 64 * 64, mask_page = r256(mask_step * (size_t)g.out_h);
     const bool large = morph != 0 && std::abs(morph) > kMorphMaxFusedRadius;
-    const int chunk = std::min(n, std::max(1, fused_max_pages(tp)));
-    const size_t masks = morph != 0 ? mask_page * (size_t)chunk * (large ? 2 : 1) : 0;
-    const size_t fused_bytes = r256(fused_small_bytes(chunk));
-    const size_t tab_bytes = r256(sizeof(void*) * (size_t)n), glob_bytes = r256(sizeof(PageGlobals) * (size_t)n);
-    // [byte masks x chunk (morph != 0)][second mask buffer (large radii)][fused work area][PageGlobals x n][src table][dst table]
-    st = ws_grow(&ws->scratch, &ws->scratch_bytes, masks + fused_bytes + glob_bytes + 2 * tab_bytes, ws->stream);
+    const size_t mask_pp = morph != 0 ? mask_page * (large ? 2 : 1) : 0;   // mask bytes per page of a chunk
+    // the kind sets the pages per chunk and the threshold step's own work area
+    const size_t lit = r256(literal_scratch_per_page(tp));
+    const int chunk = exact ? std::min(n, std::max(1, fused_max_pages(tp)))
+                            : (int)std::max<size_t>(1, std::min<size_t>((size_t)n, literal_scratch_budget() / (lit + mask_pp)));
+    const size_t work = exact ? r256(fused_small_bytes(chunk)) : lit * (size_t)chunk, masks = mask_pp * (size_t)chunk;
+    const SlotLayout tl = slot_layout(n);
+    // literal: [literal integral planes x chunk][byte masks x chunk (morph != 0)][second mask buffer (large radii)] ...
+    // exact:   [byte masks x chunk (morph != 0)][second mask buffer (large radii)][fused work area] ...
+    // both:    ... [PageGlobals x n][src table][dst table]
+    st = ws_grow(&ws->scratch, &ws->scratch_bytes, work + masks + tl.total, ws->stream);
     if (st != PRL_OK) return st;
     auto* base = static_cast<uint8_t*>(ws->scratch);
-    uint8_t* d_mask = base;
+    uint8_t* d_work = base + (exact ? masks : 0);
+    uint8_t* d_mask = base + (exact ? 0 : work);
     uint8_t* d_mask2 = d_mask + mask_page * (size_t)chunk;
-    uint8_t* d_fused = base + masks;
-    auto* d_g = reinterpret_cast<PageGlobals*>(d_fused + fused_bytes);
-    auto** d_src_tab = reinterpret_cast<const uint8_t**>(d_fused + fused_bytes + glob_bytes);
-    auto** d_dst_tab = reinterpret_cast<uint8_t**>(d_fused + fused_bytes + glob_bytes + tab_bytes);
-    std::vector<const uint8_t*> h_src((size_t)n);
-    std::vector<uint8_t*> h_dst((size_t)n);
-    for (int j = 0; j < n; ++j) {
-        const size_t i = (size_t)idx[(size_t)j];
-        h_src[(size_t)j] = pc.src_tab.empty() ? pc.src.base + i * pc.src.page_stride : pc.src_tab[i];
-        h_dst[(size_t)j] = pc.dst_tab.empty() ? pc.dst.base + i * pc.dst.page_stride : pc.dst_tab[i];
+    uint8_t* tail = base + work + masks;
+    auto* d_g = reinterpret_cast<PageGlobals*>(tail);
+    auto** d_src_tab = reinterpret_cast<const uint8_t**>(tail + tl.globals_bytes);
+    auto** d_dst_tab = reinterpret_cast<uint8_t**>(tail + tl.globals_bytes + tl.table_bytes);
+    {
+        std::vector<const uint8_t*> h_src((size_t)n);
+        std::vector<uint8_t*> h_dst((size_t)n);
+        for (int j = 0; j < n; ++j) {
+            const size_t i = (size_t)idx[(size_t)j];
+            h_src[(size_t)j] = pc.src_tab.empty() ? pc.src.base + i * pc.src.page_stride : pc.src_tab[i];
+            h_dst[(size_t)j] = pc.dst_tab.empty() ? pc.dst.base + i * pc.dst.page_stride : pc.dst_tab[i];
+        }
+        PRL_HIP_CHECK(hipMemcpyAsync(d_src_tab, h_src.data(), sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
+        PRL_HIP_CHECK(hipMemcpyAsync(d_dst_tab, h_dst.data(), sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
+        PRL_HIP_CHECK(hipStreamSynchronize(ws->stream));   // (the host vectors go out of scope; pageable memory)
     }
-    PRL_HIP_CHECK(hipMemcpyAsync(d_src_tab, h_src.data(), sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
-    PRL_HIP_CHECK(hipMemcpyAsync(d_dst_tab, h_dst.data(), sizeof(void*) * (size_t)n, hipMemcpyHostToDevice, ws->stream));
-    PRL_HIP_CHECK(hipStreamSynchronize(ws->stream));   // (the host vectors go out of scope; pageable memory)
+    if (!exact) {
+        st = init_globals_run(d_g, n, ws->stream);
+        if (st != PRL_OK) return st;
+    }
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int cnt = std::min(chunk, n - c0);
-        st = init_globals_run(d_g + c0, cnt, ws->stream, d_fused);   // (+ the counter block)
-        if (st != PRL_OK) return st;
-        PageSet src{};
-        src.table = d_src_tab + c0;
-        src.step = pc.src.step;
-        PageSetOut out{};
-        out.table = d_dst_tab + c0;
-        out.step = pc.dst.step;
-        PageSetOut thr = out;
-        if (morph != 0) {
-            thr = PageSetOut{};
-            thr.base = d_mask;
-            thr.page_stride = mask_page;
-            thr.step = mask_step;
+        const PageSet src = page_table(d_src_tab + c0, pc.src.step);
+        const PageSetOut out = page_table_out(d_dst_tab + c0, pc.dst.step);
+        const PageSetOut thr = morph != 0 ? page_set_out(d_mask, mask_page, mask_step) : out;
+        if (exact) {
+            st = init_globals_run(d_g + c0, cnt, ws->stream, d_work);   // (+ the counter block)
+            if (st != PRL_OK) return st;
+            FusedCall fc;
+            fc.tp = tp; fc.src = src; fc.dst = thr; fc.n_pages = cnt;
+            fc.small = d_work; fc.d_globals = d_g + c0; fc.stream = ws->stream;
+            fc.counters_zeroed = true;
+            fc.wolf_side = (tp.method == PRL_WOLFJOLION && ws->wolf.stream) ? &ws->wolf : nullptr;
+            fc.exact = true;
+            st = fused_run(fc);
+        } else {
+            if (tp.method == PRL_WOLFJOLION || tp.method == PRL_FENG) {
+                st = page_min_run(tp, src, cnt, d_g + c0, ws->stream);
+                if (st != PRL_OK) return st;
+            }
+            st = literal_run(tp, src, 0, cnt, thr, d_work, d_g + c0, ws->stream);
         }
-        const WolfSide* wolf_side = (tp.method == PRL_WOLFJOLION && ws->wolf.stream) ? &ws->wolf : nullptr;
-        st = fused_run(tp, src, cnt, thr, d_fused, d_g + c0, ws->stream, nullptr, nullptr, false, true, nullptr, wolf_side, true);
         if (st != PRL_OK) return st;
         if (morph == 0) continue;
-        PageSet msrc{};
-        msrc.base = d_mask;
-        msrc.page_stride = mask_page;
-        msrc.step = mask_step;
-        if (!large) st = morph_binary_run(morph, msrc, cnt, g.out_w, g.out_h, out, ws->stream);
-        else st = morph_large_run(morph, msrc, cnt, g.out_w, g.out_h, out, d_mask2, mask_step, ws->stream);
+        st = morph_from_mask(morph, thr, false, cnt, g.out_w, g.out_h, out, d_mask2, mask_step, ws->stream);
         if (st != PRL_OK) return st;
     }
+    if (!exact) return PRL_OK;
     std::vector<PageGlobals> hg((size_t)n);
     PRL_HIP_CHECK(hipMemcpyAsync(hg.data(), d_g, sizeof(PageGlobals) * (size_t)n, hipMemcpyDeviceToHost, ws->stream));
     PRL_HIP_CHECK(hipStreamSynchronize(ws->stream));
@@ -777,7 +754,7 @@ int resolve_front(StreamWs* ws)
     ws->last = cs;
     if (!second.empty()) {
         ws->clean_pages = 0;   // (the stream's state is no longer what the last call's epilogue left)
-        const int st2 = redo_pages_exact(ws, pc, second, &flagged, &cs);
+        const int st2 = redo_pages(ws, pc, second, &flagged, &cs);
         if (st2 != PRL_OK) return st2;
         std::sort(flagged.begin(), flagged.end());
     }
@@ -789,7 +766,7 @@ int resolve_front(StreamWs* ws)
                          std::to_string(budget) + " (first: page " + std::to_string(flagged.front()) + ")");
         return PRL_ERR_LITERAL_BUDGET;
     }
-    return redo_pages_literal(ws, pc, flagged);
+    return redo_pages(ws, pc, flagged);
 }
 
 int resolve_all(StreamWs* ws)
@@ -921,10 +898,7 @@ int binarize_common(const prl_binarize_params* p, int n_pages, PageSet src, int 
         const size_t first = bit_mask ? bit_page * (size_t)n_pages : mask_page * (size_t)n_pages;
         st = ws_grow(&ws->mask, &ws->mask_bytes, first + (large_morph ? mask_page * (size_t)n_pages : 0), stream);
         if (st != PRL_OK) return st;
-        thr_dst = PageSetOut{};
-        thr_dst.base = static_cast<uint8_t*>(ws->mask);
-        thr_dst.page_stride = bit_mask ? bit_page : mask_page;
-        thr_dst.step = bit_mask ? bit_step : mask_step;
+        thr_dst = page_set_out(static_cast<uint8_t*>(ws->mask), bit_mask ? bit_page : mask_page, bit_mask ? bit_step : mask_step);
     }
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -952,25 +926,19 @@ int binarize_common(const prl_binarize_params* p, int n_pages, PageSet src, int 
         // the last two find their queues on the device and do nothing when they are empty.  Pages whose fix-up queue
         // overflowed are flagged; the flags travel to the pinned slot and are looked at in resolve_front().
         auto* h_globals = reinterpret_cast<PageGlobals*>(pin + 2 * sl.table_bytes);
-        const WolfSide* wolf_side = nullptr;
+        FusedCall fc;
+        fc.tp = tp; fc.src = src; fc.dst = thr_dst; fc.n_pages = n_pages;
+        fc.small = d_fused; fc.d_globals = d_globals; fc.stream = stream;
+        fc.ev_start = ev0; fc.ev_stop = ev1;
+        fc.bit_out = bit_mask;
+        fc.counters_zeroed = true;
+        fc.host_globals = epilogue ? h_globals : nullptr;
         if (tp.method == PRL_WOLFJOLION && env_knobs().wolf_side) {
-            if (!ws->wolf.stream) {
-                // built in a local and published only when the stream and all four events exist: a half-made side would be
-                // taken for a whole one by the next call (stream set, events null)
-                WolfSide side{};
-                hipError_t e = hipStreamCreateWithFlags(&side.stream, hipStreamNonBlocking);
-                for (hipEvent_t* ev : {&side.ev_fork, &side.ev_min, &side.ev_a, &side.ev_coeff})
-                    if (e == hipSuccess) e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
-                if (e != hipSuccess) {
-                    for (hipEvent_t ev : {side.ev_fork, side.ev_min, side.ev_a, side.ev_coeff}) if (ev) (void)hipEventDestroy(ev);
-                    if (side.stream) (void)hipStreamDestroy(side.stream);
-                    PRL_HIP_CHECK(e);
-                }
-                ws->wolf = side;
-            }
-            wolf_side = &ws->wolf;
+            st = ws_wolf_side(ws);
+            if (st != PRL_OK) return st;
+            fc.wolf_side = &ws->wolf;
         }
-        st = fused_run(tp, src, n_pages, thr_dst, d_fused, d_globals, stream, ev0, ev1, bit_mask, true, epilogue ? h_globals : nullptr, wolf_side);
+        st = fused_run(fc);
         if (st != PRL_OK) return st;
         if (epilogue) ws->clean_pages = n_pages;
         else PRL_HIP_CHECK(hipMemcpyAsync(h_globals, d_globals, sizeof(PageGlobals) * (size_t)n_pages, hipMemcpyDeviceToHost, stream));
@@ -990,18 +958,8 @@ int binarize_common(const prl_binarize_params* p, int n_pages, PageSet src, int 
     }
 
     if (morph != 0) {
-        PageSet msrc{};
-        msrc.base = thr_dst.base;
-        msrc.page_stride = thr_dst.page_stride;
-        msrc.step = thr_dst.step;
-        if (bit_mask) {
-            st = morph_bitplane_run(morph, msrc, n_pages, g.out_w, g.out_h, dst, stream);
-        } else if (!large_morph) {
-            st = morph_binary_run(morph, msrc, n_pages, g.out_w, g.out_h, dst, stream);
-        } else {  // large radii: chained single-operator passes through one more page-sized buffer
-            st = morph_large_run(morph, msrc, n_pages, g.out_w, g.out_h, dst,
-                                 static_cast<uint8_t*>(ws->mask) + mask_page * (size_t)n_pages, mask_step, stream);
-        }
+        st = morph_from_mask(morph, thr_dst, bit_mask, n_pages, g.out_w, g.out_h, dst,
+                             static_cast<uint8_t*>(ws->mask) + mask_page * (size_t)n_pages, mask_step, stream);
         if (st != PRL_OK) return st;
     }
     if (ev0) PRL_HIP_CHECK(hipEventRecord(ws->call_stop, stream));
@@ -1039,6 +997,21 @@ int pages_per_call(const prl_binarize_params* p, int width, int height)
     if (prl_hip::geometry_impl(p, width, height, &g) != PRL_OK) return kMaxPagesPerLaunch;  // the error surfaces in binarize_common
     const ThrParams tp = prl_hip::make_thr_params(p, g, width, height);
     return std::max(1, std::min(kMaxPagesPerLaunch, fused_max_pages(tp)));
+}
+
+// Milliseconds between two of the profiling events of this thread's last binarize call (prl_hip_set_profiling).
+int last_elapsed_ms(float* ms, hipEvent_t StreamWs::*start, hipEvent_t StreamWs::*stop)
+{
+    if (!ms) return PRL_ERR_BAD_ARG;
+    *ms = 0.0f;
+    if (!t_last.valid) return PRL_ERR_BAD_ARG;
+    PRL_HIP_CHECK(hipSetDevice(t_last.device));
+    StreamWs* ws = stream_ws(device_ctx(t_last.device), t_last.stream);
+    std::lock_guard<std::mutex> lk(ws->mu);
+    if (!ws->prof_valid) return PRL_ERR_BAD_ARG;
+    PRL_HIP_CHECK(hipEventSynchronize(ws->*stop));
+    PRL_HIP_CHECK(hipEventElapsedTime(ms, ws->*start, ws->*stop));
+    return PRL_OK;
 }
 }
 
@@ -1112,33 +1085,9 @@ int prl_hip_set_profiling(int enabled)
     return PRL_OK;
 }
 
-int prl_hip_last_kernel_ms(float* ms)
-{
-    if (!ms) return PRL_ERR_BAD_ARG;
-    *ms = 0.0f;
-    if (!t_last.valid) return PRL_ERR_BAD_ARG;
-    PRL_HIP_CHECK(hipSetDevice(t_last.device));
-    StreamWs* ws = stream_ws(device_ctx(t_last.device), t_last.stream);
-    std::lock_guard<std::mutex> lk(ws->mu);
-    if (!ws->prof_valid) return PRL_ERR_BAD_ARG;
-    PRL_HIP_CHECK(hipEventSynchronize(ws->prof_stop));
-    PRL_HIP_CHECK(hipEventElapsedTime(ms, ws->prof_start, ws->prof_stop));
-    return PRL_OK;
-}
+int prl_hip_last_kernel_ms(float* ms) { return last_elapsed_ms(ms, &StreamWs::prof_start, &StreamWs::prof_stop); }
 
-int prl_hip_last_call_ms(float* ms)
-{
-    if (!ms) return PRL_ERR_BAD_ARG;
-    *ms = 0.0f;
-    if (!t_last.valid) return PRL_ERR_BAD_ARG;
-    PRL_HIP_CHECK(hipSetDevice(t_last.device));
-    StreamWs* ws = stream_ws(device_ctx(t_last.device), t_last.stream);
-    std::lock_guard<std::mutex> lk(ws->mu);
-    if (!ws->prof_valid) return PRL_ERR_BAD_ARG;
-    PRL_HIP_CHECK(hipEventSynchronize(ws->call_stop));
-    PRL_HIP_CHECK(hipEventElapsedTime(ms, ws->call_start, ws->call_stop));
-    return PRL_OK;
-}
+int prl_hip_last_call_ms(float* ms) { return last_elapsed_ms(ms, &StreamWs::call_start, &StreamWs::call_stop); }
 
 int prl_hip_set_deferred_completion(int enabled)
 {
@@ -1254,23 +1203,14 @@ int prl_hip_binarize_batch_device(const prl_binarize_params* p, int n_pages, con
                                   size_t src_page_stride, size_t src_step, int width, int height,
                                   uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    PageSet s{};
-    s.base = d_src;
-    s.page_stride = src_page_stride;
-    s.step = src_step;
-    PageSetOut d{};
-    d.base = d_dst;
-    d.page_stride = dst_page_stride;
-    d.step = dst_step;
+    const PageSet s = page_set(d_src, src_page_stride, src_step);
+    const PageSetOut d = page_set_out(d_dst, dst_page_stride, dst_step);
     // (prl_hip_last_stats then describes the last chunk)
     const int per_call = pages_per_call(p, width, height);
     for (int first = 0; first < n_pages || first == 0; first += per_call) {
         const int cnt = std::min(per_call, n_pages - first);
-        PageSet sc = s;
-        PageSetOut dc = d;
-        sc.base = d_src ? d_src + (size_t)first * src_page_stride : nullptr;
-        dc.base = d_dst ? d_dst + (size_t)first * dst_page_stride : nullptr;
-        const int st = binarize_common(p, cnt, sc, width, height, dc, nullptr, nullptr, static_cast<hipStream_t>(stream));
+        const int st = binarize_common(p, cnt, pages_from(s, first), width, height, pages_from(d, first), nullptr, nullptr,
+                                       static_cast<hipStream_t>(stream));
         if (st != PRL_OK || n_pages <= 0) return st;
     }
     return PRL_OK;
@@ -1281,10 +1221,8 @@ int prl_hip_binarize_pages_device(const prl_binarize_params* p, int n_pages,
                                   int height, uint8_t* const* d_dst_pages, size_t dst_step, void* stream)
 {
     if (n_pages > 0 && (!d_src_pages || !d_dst_pages)) return PRL_ERR_BAD_ARG;
-    PageSet s{};
-    s.step = src_step;
-    PageSetOut d{};
-    d.step = dst_step;
+    const PageSet s = page_table(nullptr, src_step);   // (binarize_common points them at its device copies of the tables)
+    const PageSetOut d = page_table_out(nullptr, dst_step);
     const int per_call = pages_per_call(p, width, height);
     for (int first = 0; first < n_pages || first == 0; first += per_call) {
         const int cnt = std::min(per_call, n_pages - first);
@@ -1357,14 +1295,8 @@ int prl_hip_morph_batch_device(int morph_iterations, int n_pages, const uint8_t*
                                            static_cast<hipStream_t>(stream)));
         return PRL_OK;
     }
-    PageSet s{};
-    s.base = d_src;
-    s.page_stride = src_page_stride;
-    s.step = src_step;
-    PageSetOut d{};
-    d.base = d_dst;
-    d.page_stride = dst_page_stride;
-    d.step = dst_step;
+    const PageSet s = page_set(d_src, src_page_stride, src_step);
+    const PageSetOut d = page_set_out(d_dst, dst_page_stride, dst_step);
     if (std::abs(morph_iterations) <= kMorphMaxFusedRadius)
         return morph_run(morph_iterations, s, n_pages, width, height, d, static_cast<hipStream_t>(stream));
     DeviceCtx* ctx = device_ctx(dev);

@@ -234,6 +234,20 @@ struct PageSetOut {
         return table ? table[i] : base + (size_t)i * page_stride;
     }
 };
+// Host helpers (free functions: both sets are kernel arguments and stay plain aggregates).  page_table*: `table` is a DEVICE array.
+inline PageSet page_set(const uint8_t* base, size_t page_stride, size_t step) { return PageSet{base, page_stride, nullptr, step}; }
+inline PageSetOut page_set_out(uint8_t* base, size_t page_stride, size_t step) { return PageSetOut{base, page_stride, nullptr, step}; }
+inline PageSet page_table(const uint8_t* const* table, size_t step) { return PageSet{nullptr, 0, table, step}; }
+inline PageSetOut page_table_out(uint8_t* const* table, size_t step) { return PageSetOut{nullptr, 0, table, step}; }
+inline PageSet as_source(const PageSetOut& d) { return PageSet{d.base, d.page_stride, d.table, d.step}; }   // an output set re-read
+// the same set starting `first` pages later (a null base stays null: the entry checks answer for it)
+template <typename Set>
+inline Set pages_from(Set s, int first)
+{
+    if (s.table) s.table += first;
+    else if (s.base) s.base += (size_t)first * s.page_stride;
+    return s;
+}
 
 // Threshold constants shared by the literal and fused kernels (host-prepared, passed by value).
 struct ThrParams {
@@ -250,6 +264,7 @@ struct ThrParams {
     double k2;     // Feng
     double gamma;  // Feng
 };
+ThrParams make_thr_params(const prl_binarize_params* p, const prl_binarize_geometry& g, int width, int height);   // prl_capi.hip
 
 // Per-page globals living in device memory (Wolf-Jolion / Feng reductions, fix-up bookkeeping).
 struct PageGlobals {
@@ -291,12 +306,22 @@ struct WolfSide {
     hipEvent_t ev_fork = nullptr, ev_min = nullptr, ev_a = nullptr, ev_coeff = nullptr;
 };
 size_t fused_small_bytes(int n_pages);
-// bit_out: dst is a bit plane (rows of dst.step bytes, 1 bit per output pixel) instead of a 0/255 byte mask
-int fused_run(const ThrParams& tp, const PageSet& src, int n_pages, const PageSetOut& dst,
-              void* small, PageGlobals* d_globals, hipStream_t stream, hipEvent_t ev_start,
-              hipEvent_t ev_stop, bool bit_out = false, bool counters_zeroed = false,
-              PageGlobals* host_globals = nullptr, const WolfSide* wolf_side = nullptr,   // host_globals (pinned, n_pages entries): see FusedParams::ep_host
-              bool exact = false);   // exact: the second chance of flagged pages (k_fused_exact: the float64 interval test inline, no queue)
+struct FusedCall {   // the arguments of fused_run, filled by field name
+    ThrParams tp{};
+    PageSet src{};
+    PageSetOut dst{};
+    int n_pages = 0;
+    void* small = nullptr;               // the fused work area, fused_small_bytes(n_pages) bytes
+    PageGlobals* d_globals = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // optional: recorded around the threshold sweep
+    bool bit_out = false;                // dst is a bit plane (rows of dst.step bytes, 1 bit per output pixel) instead of a 0/255 byte mask
+    bool counters_zeroed = false;        // the counter block at the start of `small` is already zero
+    PageGlobals* host_globals = nullptr; // (pinned, n_pages entries): see FusedParams::ep_host
+    const WolfSide* wolf_side = nullptr;
+    bool exact = false;                  // the second chance of flagged pages (k_fused_exact: the float64 interval test inline, no queue)
+};
+int fused_run(const FusedCall& c);
 bool fused_supports(const ThrParams& tp);
 int fused_max_pages(const ThrParams& tp);  // pages one fused_run call can take (Wolf-Jolion: per-wavefront maxima storage)
 

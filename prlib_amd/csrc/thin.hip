@@ -336,14 +336,8 @@ int thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_
     auto* act1 = act0 + act_cap;
     PRL_HIP_CHECK(hipMemsetAsync(act0, 1, act_cap, s));  // before the first pass every tile counts as changed
 
-    PageSet ps{};
-    ps.base = d_src;
-    ps.page_stride = src_page_stride;
-    ps.step = src_step;
-    PageSetOut pd{};
-    pd.base = d_dst;
-    pd.page_stride = dst_page_stride;
-    pd.step = dst_step;
+    const PageSet ps = page_set(d_src, src_page_stride, src_step);
+    const PageSetOut pd = page_set_out(d_dst, dst_page_stride, dst_step);
     const dim3 gw((unsigned)((plane_words + 255) / 256), n_pages);  // one thread per 32-pixel word
     hipLaunchKernelGGL(k_thin_pack, gw, dim3(256), 0, s, ps, width, height, wpr, A, plane_words, invert_input ? 0xffffffffu : 0u);
     PRL_HIP_CHECK(hipGetLastError());
