@@ -382,6 +382,48 @@ int prl_hip_median_batch_device(int n_pages, int channels, int ksize, size_t tim
 int prl_hip_median_host(int channels, int ksize, size_t times, const uint8_t* src, size_t src_step, int width, int height,
                         uint8_t* dst, size_t dst_step);
 
+/* ---- grayscale morphology with a flat element, prl::correctNUIL ----------------------------------------------------- */
+
+#define PRL_MORPH_ERODE 0     /* cv::MORPH_ERODE */
+#define PRL_MORPH_DILATE 1    /* cv::MORPH_DILATE */
+#define PRL_MORPH_OPEN 2      /* cv::MORPH_OPEN: erode, then dilate */
+#define PRL_MORPH_CLOSE 3     /* cv::MORPH_CLOSE: dilate, then erode */
+#define PRL_MORPH_TOPHAT 5    /* cv::MORPH_TOPHAT: src - open, saturating */
+#define PRL_MORPH_BLACKHAT 6  /* cv::MORPH_BLACKHAT: close - src, saturating */
+#define PRL_SHAPE_RECT 0      /* cv::MORPH_RECT */
+#define PRL_SHAPE_CROSS 1     /* cv::MORPH_CROSS */
+#define PRL_SHAPE_ELLIPSE 2   /* cv::MORPH_ELLIPSE */
+
+/*
+ * cv::morphologyEx(src, dst, op, cv::getStructuringElement(shape, Size(ksize_w, ksize_h))), one iteration, on 8-bit pages of
+ * 1..4 interleaved channels in device memory: dst(y, x, c) = min (erode) / max (dilate) over the element's set pixels (i, j)
+ * of src(y + i - ksize_h/2, x + j - ksize_w/2, c); taps outside the page are ignored (morphologyDefaultBorderValue) and the
+ * element is not reflected between the two operators.  Exact.  Element sizes 1..255 each way (OpenCV has no upper limit);
+ * width, height <= 32768.  d_src == d_dst with the same strides (in place) is allowed; any other overlap returns
+ * PRL_ERR_BAD_ARG, and d_src is otherwise never written.  Intermediate planes (at most two of width * channels * height bytes
+ * per page) live in the device's cached scratch.  Enqueues on `stream`, no synchronisation.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_ARG (unknown op or
+ * shape, a size < 1 or > 255); PRL_ERR_BAD_CHANNELS (channels outside 1..4); PRL_ERR_BAD_ARG (null pointer, negative n_pages,
+ * step < row bytes, width or height above the limit, overlapping source and destination).
+ */
+int prl_hip_morphology_batch_device(int n_pages, int channels, int op, int shape, int ksize_w, int ksize_h, const uint8_t* d_src,
+                                    size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                    size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_morphology_host(int channels, int op, int shape, int ksize_w, int ksize_h, const uint8_t* src, size_t src_step, int width,
+                            int height, uint8_t* dst, size_t dst_step);
+
+/*
+ * prl::correctNUIL(in, out, structuringElementSize = 31) (src/correctNUIL.cpp:33-90): per page and channel, the channel is
+ * inverted (x ^ 255) where its mean over the page is below 128 (decided on the device as sum < 128 * width * height), then
+ * dst = 255 - blackhat(channel, ellipse(size, size)).  Same layouts, aliasing rule, limits, stream semantics and order of the
+ * checks as prl_hip_morphology_batch_device (size < 1 or > 255: PRL_ERR_BAD_ARG).
+ */
+int prl_hip_correct_nuil_batch_device(int n_pages, int channels, int size, const uint8_t* d_src, size_t src_page_stride,
+                                      size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                      void* stream);
+int prl_hip_correct_nuil_host(int channels, int size, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
+                              size_t dst_step);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

@@ -13,6 +13,7 @@
 //   src/binarizations/binarizeNativeAdaptive.h:62-74       prl::binarizeNativeAdaptive
 //   src/binarizations/binarizeAT.h:33, binarizeAGT.h:32    prl::binarizeAT, prl::binarizeAGT
 //   src/binarizations/binarizePureAdaptiveGaussian.h:33    prl::binarizePureAdaptiveGaussian
+//   src/correctNUIL.h:32                                   prl::correctNUIL
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -93,6 +94,14 @@ CV_EXPORTS void binarizeAGT(const cv::Mat& inputImage, cv::Mat& outputImage, con
                  const int blockSize, const int shift);
 CV_EXPORTS void binarizePureAdaptiveGaussian(const cv::Mat& inputImage, cv::Mat& outputImage, const double maxValue,
                                   const int blockSize, const int shift);
+
+// src/correctNUIL.h:32 - removes non-uniform illumination (correctNUIL.cpp:33-90): per channel, x ^ 255 where cv::mean over the
+// page is below 128, then 255 - cv::morphologyEx(channel, MORPH_BLACKHAT, getStructuringElement(MORPH_ELLIPSE, Size(size, size))).
+// std::invalid_argument("Input image for filtration is empty"); cv::Exception: StsAssert for more than 4 channels (cv::mean) and
+// for structuringElementSize < 1 (getStructuringElement), StsUnsupportedFormat for a depth other than CV_8U, StsBadArg for a
+// size above 255 (OpenCV has no upper limit: not here).  The output is a new continuous Mat of the input's size and type; the
+// input's pixels are never written (out may be in, or a view of it).
+CV_EXPORTS void correctNUIL(const cv::Mat& inputImage, cv::Mat& outputImage, int structuringElementSize = 31);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

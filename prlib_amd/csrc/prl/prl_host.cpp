@@ -184,6 +184,22 @@ void prl::denoiseSaltPepper(const cv::Mat& in, cv::Mat& out, int kernelSize, siz
     out = result;
 }
 
+// correctNUIL.cpp:55-90.  The reference's order: the empty check, cv::mean (at most 4 channels), then per channel
+// getStructuringElement's assertion on the size before cv::morphologyEx runs.
+void prl::correctNUIL(const cv::Mat& inputImage, cv::Mat& outputImage, int structuringElementSize)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image for filtration is empty");
+    if (inputImage.channels() > 4) PRL_FAIL_CV(cv::Error::StsAssert, "cn <= 4");                       // [upstream] cv::mean
+    if (inputImage.depth() != CV_8U)
+        PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::correctNUIL: 8-bit images only");          // documented deviation
+    if (structuringElementSize < 1) PRL_FAIL_CV(cv::Error::StsAssert, "ksize.width > 0 && ksize.height > 0");
+    cv::Mat result(inputImage.rows, inputImage.cols, inputImage.type());
+    const int st = prl_hip_correct_nuil_host(inputImage.channels(), structuringElementSize, inputImage.data, inputImage.step,
+                                             inputImage.cols, inputImage.rows, result.data, result.step);
+    if (st != PRL_OK) raise(st);   // a size above 255: StsBadArg
+    outputImage = result;
+}
+
 namespace {
 
 constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255

@@ -40,7 +40,7 @@ struct DeviceCtx {
     ~DeviceCtx();
     std::mutex mu;          // one call at a time per device on the shared workspace (scratch, small, pinned)
     int device = -1;
-    void* scratch = nullptr;   // page-sized work planes of the batch entries (bgnorm, LV, thinning, NL-means, median, morph)
+    void* scratch = nullptr;   // page-sized work planes of the batch entries (bgnorm, LV, thinning, NL-means, median, morph, gmorph)
     size_t scratch_bytes = 0;
     void* small = nullptr;  // counters / work lists / per-page globals
     size_t small_bytes = 0;
@@ -128,6 +128,7 @@ struct EnvKnobs {
     unsigned segmax_cap = 1u << 20;     // PRL_HIP_SEGMAX_CAP   wavefronts per Wolf-Jolion call (tests shrink it)
     int literal_mode = 0;         // PRL_HIP_MODE=literal
     bool median_generic = false;  // PRL_HIP_MEDIAN_GENERIC=1  the histogram kernel for every window (median.hip), k = 3 and 5 included
+    bool gmorph_literal = false;  // PRL_HIP_GMORPH_LITERAL=1  the by-the-definition kernel for every element (gmorph.hip)
 };
 const EnvKnobs& env_knobs();
 
