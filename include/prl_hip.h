@@ -104,7 +104,8 @@ typedef enum prl_exec_mode {
     PRL_MODE_LITERAL = 1   /* materialised float64 integral images, one literal evaluation per pixel */
 } prl_exec_mode;
 
-/* Counters of the last binarize call on the calling thread (for tests and the bench report). */
+/* Counters of the last binarize call on the calling thread (for tests and the bench report).  Every page counts once, in
+ * the pass that wrote its final bytes; a call that was split into page chunks reports the sum of its chunks. */
 typedef struct prl_binarize_stats {
     uint64_t pixels;            /* output pixels produced */
     uint64_t refined_pixels;    /* decided by the in-kernel float64 interval test instead of the float32 one */

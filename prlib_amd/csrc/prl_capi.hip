@@ -111,6 +111,7 @@ const EnvKnobs& env_knobs()
         k.median_generic = geti("PRL_HIP_MEDIAN_GENERIC", 0) != 0;
         k.gmorph_literal = geti("PRL_HIP_GMORPH_LITERAL", 0) != 0;
         k.segmax_cap = (unsigned)std::max(64ll, std::min(1ll << 20, geti("PRL_HIP_SEGMAX_CAP", 1 << 20)));
+        k.force_exact = geti("PRL_HIP_FORCE_EXACT", 0) != 0;
 #endif
         return k;
     }();
@@ -136,10 +137,19 @@ struct PendingCall {
     std::vector<const uint8_t*> src_tab;  // ... or host copies of the page tables
     std::vector<uint8_t*> dst_tab;
     uint64_t pixels = 0;
+    bool continues = false;   // a later page chunk of one entry call (pages_per_call): its statistics go on top of the chunk's before it
 };
 
 struct CallStats {
     uint64_t seq = 0, pixels = 0, refined = 0, exact = 0, literal_pages = 0, wolf_candidates = 0, exact_sweep_pages = 0;
+    // A later chunk of an entry call takes over what the call's earlier chunks counted (they carry the sequence number before it,
+    // unless another thread's call on the same stream came between: then the chunk stands alone).
+    void carry(const CallStats& prev)
+    {
+        if (prev.seq + 1 != seq) return;
+        pixels += prev.pixels; refined += prev.refined; exact += prev.exact; literal_pages += prev.literal_pages;
+        wolf_candidates += prev.wolf_candidates; exact_sweep_pages += prev.exact_sweep_pages;
+    }
 };
 
 struct StreamWs {
@@ -689,6 +699,8 @@ int redo_pages(StreamWs* ws, const PendingCall& pc, const std::vector<int>& idx,
         st = init_globals_run(d_g, n, ws->stream);
         if (st != PRL_OK) return st;
     }
+    // (exact: always ONE chunk through the C entries - they cut a call at pages_per_call(), the same fused_max_pages(tp) - so the
+    // c0 > 0 rounds below are the literal redo's; no test can reach them in exact mode)
     for (int c0 = 0; c0 < n; c0 += chunk) {
         const int cnt = std::min(chunk, n - c0);
         const PageSet src = page_table(d_src_tab + c0, pc.src.step);
@@ -721,9 +733,11 @@ int redo_pages(StreamWs* ws, const PendingCall& pc, const std::vector<int>& idx,
     PRL_HIP_CHECK(hipMemcpyAsync(hg.data(), d_g, sizeof(PageGlobals) * (size_t)n, hipMemcpyDeviceToHost, ws->stream));
     PRL_HIP_CHECK(hipStreamSynchronize(ws->stream));
     for (int j = 0; j < n; ++j) {
+        // (a page counts once, in the pass that wrote its final bytes: this one, unless the literal pipeline still has to redo it)
+        if (hg[(size_t)j].worklist_overflow) { still->push_back(idx[(size_t)j]); continue; }
         cs->refined += hg[(size_t)j].n_refined;
         cs->exact += hg[(size_t)j].n_exact;
-        if (hg[(size_t)j].worklist_overflow) still->push_back(idx[(size_t)j]);
+        cs->wolf_candidates += hg[(size_t)j].n_cand;
     }
     return PRL_OK;
 }
@@ -743,15 +757,21 @@ int resolve_front(StreamWs* ws)
     cs.pixels = pc.pixels;
     // Flagged pages.  Bit 0 alone: the refine queue overflowed - the exact sweep redoes the page (a few times a page's usual
     // cost, not bounded by the literal budget).  Bit 1 (then, or after that sweep): the fix-up list overflowed - the literal pipeline.
+    // The counters of prl_hip_last_stats take every page once, from the pass that wrote its final bytes: a page that is redone
+    // leaves its first-pass counts out (the exact sweep adds its own in redo_pages; the literal pipeline queues nothing).
+    // PRL_HIP_FORCE_EXACT (test-hooks build): every page without bit 1 takes the second chance, flagged or not - the only way
+    // Wolf-Jolion and Feng pages reach the exact sweep on demand (they have no closed-form adversarial input).
+    const bool force_exact = env_knobs().force_exact;
     std::vector<int> flagged, second;
     for (int i = 0; i < pc.n_pages; ++i) {
+        if (hg[(size_t)i].worklist_overflow & 2u) { flagged.push_back(i); continue; }
+        if (hg[(size_t)i].worklist_overflow || force_exact) { second.push_back(i); continue; }
         cs.refined += hg[(size_t)i].n_refined;
         cs.exact += hg[(size_t)i].n_exact;
         cs.wolf_candidates += hg[(size_t)i].n_cand;
-        if (hg[(size_t)i].worklist_overflow & 2u) flagged.push_back(i);
-        else if (hg[(size_t)i].worklist_overflow) second.push_back(i);
     }
     cs.exact_sweep_pages = second.size();
+    if (pc.continues) cs.carry(ws->last);
     ws->last = cs;
     if (!second.empty()) {
         ws->clean_pages = 0;   // (the stream's state is no longer what the last call's epilogue left)
@@ -759,7 +779,7 @@ int resolve_front(StreamWs* ws)
         if (st2 != PRL_OK) return st2;
         std::sort(flagged.begin(), flagged.end());
     }
-    cs.literal_pages = flagged.size();
+    cs.literal_pages += flagged.size();
     ws->last = cs;
     const int budget = literal_budget();
     if (budget >= 0 && (int)flagged.size() > budget) {   // the caller's cost bound: report, do not redo
@@ -810,7 +830,7 @@ int take_slot(StreamWs* ws, int n_pages, int* slot)
 
 int binarize_common(const prl_binarize_params* p, int n_pages, PageSet src, int width, int height,
                     PageSetOut dst, const uint8_t* const* h_src_tab, uint8_t* const* h_dst_tab,
-                    hipStream_t stream)
+                    hipStream_t stream, bool continues = false)
 {
     prl_binarize_geometry g;
     int st = geometry_impl(p, width, height, &g);
@@ -864,6 +884,7 @@ int binarize_common(const prl_binarize_params* p, int n_pages, PageSet src, int 
     pc.src = src;
     pc.dst = dst;
     pc.pixels = (uint64_t)g.out_w * g.out_h * (uint64_t)n_pages;
+    pc.continues = continues;
     if (h_src_tab) {
         pc.src_tab.assign(h_src_tab, h_src_tab + n_pages);
         std::memcpy(pin, h_src_tab, sizeof(void*) * (size_t)n_pages);
@@ -955,7 +976,9 @@ int binarize_common(const prl_binarize_params* p, int n_pages, PageSet src, int 
             if (st != PRL_OK) return st;
         }
         if (ev1) PRL_HIP_CHECK(hipEventRecord(ev1, stream));
-        ws->last = CallStats{pc.seq, pc.pixels, 0, 0, (uint64_t)n_pages};
+        CallStats cs{pc.seq, pc.pixels, 0, 0, (uint64_t)n_pages};
+        if (continues) cs.carry(ws->last);
+        ws->last = cs;
     }
 
     if (morph != 0) {
@@ -1206,12 +1229,12 @@ int prl_hip_binarize_batch_device(const prl_binarize_params* p, int n_pages, con
 {
     const PageSet s = page_set(d_src, src_page_stride, src_step);
     const PageSetOut d = page_set_out(d_dst, dst_page_stride, dst_step);
-    // (prl_hip_last_stats then describes the last chunk)
+    // (prl_hip_last_stats adds the chunks up: PendingCall::continues)
     const int per_call = pages_per_call(p, width, height);
     for (int first = 0; first < n_pages || first == 0; first += per_call) {
         const int cnt = std::min(per_call, n_pages - first);
         const int st = binarize_common(p, cnt, pages_from(s, first), width, height, pages_from(d, first), nullptr, nullptr,
-                                       static_cast<hipStream_t>(stream));
+                                       static_cast<hipStream_t>(stream), first > 0);
         if (st != PRL_OK || n_pages <= 0) return st;
     }
     return PRL_OK;
@@ -1228,7 +1251,7 @@ int prl_hip_binarize_pages_device(const prl_binarize_params* p, int n_pages,
     for (int first = 0; first < n_pages || first == 0; first += per_call) {
         const int cnt = std::min(per_call, n_pages - first);
         const int st = binarize_common(p, cnt, s, width, height, d, d_src_pages ? d_src_pages + first : nullptr,
-                                       d_dst_pages ? d_dst_pages + first : nullptr, static_cast<hipStream_t>(stream));
+                                       d_dst_pages ? d_dst_pages + first : nullptr, static_cast<hipStream_t>(stream), first > 0);
         if (st != PRL_OK || n_pages <= 0) return st;
     }
     return PRL_OK;

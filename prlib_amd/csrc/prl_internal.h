@@ -126,6 +126,7 @@ struct EnvKnobs {
     int fake_devices = 0;               // PRL_HIP_FAKE_DEVICES   (tests) logical devices of the *_batch_host entries, mapped onto the real ones
     int host_copy_threads = 0;          // PRL_HIP_HOST_COPY_THREADS  threads of the pool that copies pageable pages in / out of pinned memory (0: half of the cores, at most 32)
     unsigned segmax_cap = 1u << 20;     // PRL_HIP_SEGMAX_CAP   wavefronts per Wolf-Jolion call (tests shrink it)
+    bool force_exact = false;           // PRL_HIP_FORCE_EXACT=1  (tests) every page whose fix-up list did not overflow is redone by the exact sweep (resolve_front)
     int literal_mode = 0;         // PRL_HIP_MODE=literal
     bool median_generic = false;  // PRL_HIP_MEDIAN_GENERIC=1  the histogram kernel for every window (median.hip), k = 3 and 5 included
     bool gmorph_literal = false;  // PRL_HIP_GMORPH_LITERAL=1  the by-the-definition kernel for every element (gmorph.hip)

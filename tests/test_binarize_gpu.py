@@ -37,7 +37,9 @@ def _check(prl, oracle, dev, pages_np, method, win, k, morph, feng=None, mode=No
         assert got[i].shape == wnt.shape
         bad = int((got[i] != wnt).sum())
         assert bad == 0, f"page {i}: {bad} mismatching pixels (method {method}, w {win}, k {k}, morph {morph})"
-    return prl.last_stats()
+    st = prl.last_stats()
+    assert st.refined_pixels <= st.pixels and st.exact_pixels <= st.pixels
+    return st
 
 
 def _pages(shape, kinds, seed=0):
@@ -636,11 +638,13 @@ got = prlib_amd.binarize(torch.from_numpy(pages).cuda(), p).cpu().numpy()
 po = oc.make_params(oc.WOLFJOLION, 31, 0.3, 0)
 bad = sum(int((got[i] != oc.binarize(pages[i], po)).sum()) for i in range(12))
 print("MISMATCH", bad)
+print("PIXELS", prlib_amd.last_stats().pixels)   # the statistics add the page chunks of the call up
 ''' % ROOT
     env = dict(os.environ, PRL_HIP_SEGMAX_CAP="64")
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "MISMATCH 0" in r.stdout, r.stdout + r.stderr
+    assert "PIXELS %d\n" % (12 * (200 - 31) * (1300 - 31)) in r.stdout, r.stdout + r.stderr
 
 
 def test_wide_windows_float_rows_kernel_equals_the_integer_loop_and_the_oracle():
@@ -940,3 +944,245 @@ def test_on_threshold_patch_that_fills_a_queue_bucket_does_not_take_the_literal_
     for morph in (0, 2):
         st = _check(prl, oracle, cuda_device, [other, doc], SAUVOLA, w, k, morph)
         assert st.literal_pages == 0 and st.exact_pixels >= 100 * 160, (st.literal_pages, st.exact_sweep_pages, st.exact_pixels)
+
+
+def test_counters_take_a_redone_page_once(prl, oracle, cuda_device):
+    """prl_hip_last_stats counts a page in the pass that wrote its final bytes, once.  The flat page np.full((230, 310), 200) at
+    Sauvola w = 15 with the k that puts every output pixel on its own threshold: 229 x 309 = 70 761 true ties, fewer than the
+    fix-up list holds (2^17), all of which only the literal evaluation decides.
+
+    Called alone, the page does not overflow its refine queue (profiles/r10/INDEX.md): a call this small runs row segments of
+    8 rows, a wavefront queues 8 x 309 pixels into a bucket of 8192 that it shares with nobody.  A wavefront's share passes 8192 from 27 rows of 309 columns on, and plan_segments() keeps segments of
+    32 rows once the call has 4096 wavefronts of that length: 512 pages of this size.  So the page sits among 511 flat pages of
+    value 90 (far from their threshold, 96.6 against 89.5: decided by the float32 test, nothing queued): its eight wavefronts
+    queue 9888 pixels each, the page is flagged (bit 0), the exact sweep redoes it and every one of its pixels ends in the
+    fix-up list.  Summing both passes, as the library did, reported the first pass's queued share (up to 8 x 8192) on top."""
+    import torch
+
+    w, c = 15, 200
+    k = _flat_boundary_k(c, w, c)
+    tie = np.full((230, 310), c, np.uint8)
+    st = _check(prl, oracle, cuda_device, [tie], SAUVOLA, w, k, 0)
+    print("flat on-threshold page alone:", st.pixels, st.exact_sweep_pages, st.literal_pages, st.exact_pixels, st.refined_pixels)
+    assert st.pixels == 229 * 309 and st.literal_pages == 0
+    assert st.exact_pixels == st.pixels and st.refined_pixels <= st.pixels
+    n, at = 512, 300
+    pages = np.full((n, 230, 310), 90, np.uint8)
+    pages[at] = tie
+    got = prl.binarize(torch.from_numpy(pages).to(cuda_device), prl.make_params(SAUVOLA, w, k, 0)).cpu().numpy()
+    st = prl.last_stats()
+    print("the same page among 511 flat ones:", st.pixels, st.exact_sweep_pages, st.literal_pages, st.exact_pixels, st.refined_pixels)
+    po = oracle.make_params(SAUVOLA, w, k, 0)
+    want_tie, want_other = oracle.binarize(tie, po), oracle.binarize(pages[0], po)
+    assert np.array_equal(got[at], want_tie)
+    assert (np.delete(got, at, axis=0) == want_other[None]).all()
+    assert st.pixels == n * 229 * 309
+    assert st.exact_sweep_pages == 1 and st.literal_pages == 0
+    assert st.exact_pixels == 229 * 309          # the page's pixels, once
+    assert st.refined_pixels <= st.pixels
+
+
+# ---- the exact sweep (k_fused_exact) on demand: PRL_HIP_FORCE_EXACT of the test-hooks build ---------------------------------------
+# Wolf-Jolion and Feng have no closed-form adversarial input (bench.adversarial_stripes returns None for them), so no page of theirs
+# overflows its refine queue by itself.  With the knob resolve_front() sends every page whose fix-up list did not overflow through
+# redo_pages() in exact mode.  Knobs are read once per process: children, one per setting, each run once and shared by the tests
+# below.  A child that died (signal, abort, GPU fault) fails its test and every later one without another process being started.
+_FORCED_CHILD = r'''
+import ctypes as C, json, sys, zlib
+import numpy as np, torch
+sys.path.insert(0, %(root)r)
+sys.path.insert(0, %(tests)r)
+import prlib_amd
+from prlib_amd import _capi, synth
+which = sys.argv[1]
+if which != "product":
+    _capi.use_library(_capi.HOOKS_LIB_PATH)
+from oracle import capi as oc
+import test_binarize_gpu as T
+SAUVOLA, NIBLACK, WOLFJOLION, NICK, FENG = range(5)
+KINDS = ["doc", "noise", "flat", "black", "dark_corner"]
+dev = torch.device("cuda:0")
+cases = []   # (name, group, method, w, k, morph, pages, feng, through the page-table entry)
+
+def add(name, group, method, w, k, pages, morphs=(0, 2), feng=None, table=False):
+    for morph in morphs:
+        cases.append(("%%s m%%d" %% (name, morph), group, method, w, k, morph, pages, feng or {}, table))
+
+if which in ("all", "wolf"):
+    # one border strip (w + 45 columns); interior and border strips (1100 columns: first_col + 512 <= width)
+    for method, w, k in ((SAUVOLA, 15, 0.34), (SAUVOLA, 31, 0.34), (NIBLACK, 15, -0.2), (NIBLACK, 31, 0.01), (WOLFJOLION, 15, 0.01),
+                         (WOLFJOLION, 31, 0.3), (NICK, 15, -0.01), (NICK, 31, -0.1), (FENG, 15, 0.0), (FENG, 31, 0.0)):
+        for width in (w + 45, 1100):
+            add("strips %%d w%%d %%d" %% (method, w, width), "rows", method, w, k, T._pages((300, width), KINDS, seed=method * 7 + w))
+    # the extended last strip of the integer loop (fp.ext): 456 columns are one extended strip at w = 101, 457 are two plain ones
+    for method, k in ((SAUVOLA, 0.01), (WOLFJOLION, 0.01), (FENG, 0.0)):
+        for width in (456, 457, 870):
+            add("ext %%d %%d" %% (method, width), "rows", method, 101, k, T._pages((300, width), KINDS, seed=method * 11 + width))
+    # the WIDE instantiation (w - 1 > 181)
+    for method, k in ((NIBLACK, 0.2), (WOLFJOLION, 0.3), (FENG, 0.0)):
+        add("wide %%d" %% method, "rows", method, 201, k, T._pages((300, 700), KINDS, seed=method * 13 + 201))
+    # the other shift classes (w - 1) & 7: 4, 0, 2, 6
+    for method, w, k in ((NICK, 21, -0.01), (SAUVOLA, 33, 0.2), (FENG, 51, 0.0), (WOLFJOLION, 63, 0.3)):
+        add("sh %%d w%%d" %% (method, w), "rows", method, w, k, T._pages((300, 600), KINDS, seed=method * 17 + w))
+    # Feng: both parameter sets of test_feng_parameters, a page whose minimum is 0 and one whose minimum is 40 (p0 from imin)
+    lo, hi = T._pages((203, 331), ["doc", "doc"], seed=71)
+    lo[0, 0] = 0
+    hi = np.maximum(hi, 40)
+    hi[5, 7] = 40
+    assert lo.min() == 0 and hi.min() == 40
+    for i, feng in enumerate((dict(alpha1=0.12, k1=0.25, k2=0.04, gamma=2.0), dict(alpha1=0.5, k1=0.1, k2=0.01, gamma=3.0))):
+        add("feng set %%d" %% i, "rows", FENG, 21, 0.0, [lo, hi], feng=feng)
+    # a radius above kMorphMaxFusedRadius: the redo's second mask buffer; one call through the page-table entry
+    add("morph9", "extra", WOLFJOLION, 31, 0.3, T._pages((300, 1100), KINDS, seed=73), morphs=(9,))
+    add("table", "extra", FENG, 31, 0.0, T._pages((300, 1100), KINDS, seed=74), morphs=(2,), table=True)
+    # Wolf-Jolion ties: the literal fix-up needs the literal devianceMax, computed lazily - here entered from the redo
+    page, kb, _ = T._wolf_boundary_page_and_k(oc, 15, 120, flat=24, seed=61)
+    others = T._pages(page.shape, ["doc", "noise"], seed=62)
+    add("wolf ties", "boundary", WOLFJOLION, 15, float(kb), [others[0], page, others[1]])
+    if which == "wolf":   # (the Wolf-Jolion rows of the table and the ties)
+        cases = [c for c in cases if c[2] == WOLFJOLION and c[1] in ("rows", "boundary")]
+    else:
+        # Feng's rational ties at the header defaults: 4 pages of 1536 x 1536 already hold some (about 5 pixels in 10^6)
+        ties = synth.pages_torch(4, 1536, 1536, dev, seed=4000).cpu().numpy()
+        pf = prlib_amd.default_params(FENG)
+        cases.append(("feng ties", "ties", FENG, pf.window_size, pf.k, pf.morph_iterations, list(ties), {}, False))
+elif which == "chunks":
+    pages = [synth.page_numpy(200, 1300, index=i) for i in range(12)]
+    add("chunks", "chunks", WOLFJOLION, 31, 0.3, pages)
+else:   # the product library does not know the knob
+    add("product", "product", SAUVOLA, 31, 0.34, T._pages((300, 1100), ["doc"], seed=75), morphs=(0,))
+
+# the oracle's pages on a few threads beside the device's work (the C oracle keeps no state and ctypes releases the interpreter lock)
+from concurrent.futures import ThreadPoolExecutor
+pool = ThreadPoolExecutor(8)
+wants = [[pool.submit(oc.binarize, np.ascontiguousarray(pg), oc.make_params(c[2], c[3], c[4], c[5], **c[7])) for pg in c[6]] for c in cases]
+bad, crc, rows = 0, 0, []
+for (name, group, method, w, k, morph, pages, feng, table), want in zip(cases, wants):
+    params = prlib_amd.make_params(method, w, k, morph, **feng)
+    if table:
+        h, wd = pages[0].shape
+        g = prlib_amd.geometry(params, wd, h)
+        pitch = (g.out_w + 127) // 128 * 128
+        src = [torch.from_numpy(p).to(dev) for p in pages]
+        dst = [torch.zeros((g.out_h, pitch), dtype=torch.uint8, device=dev) for _ in pages]
+        n = len(pages)
+        src_tab = (C.c_void_p * n)(*[t.data_ptr() for t in src])
+        dst_tab = (C.c_void_p * n)(*[t.data_ptr() for t in dst])
+        _capi.check(_capi.lib().prl_hip_binarize_pages_device(C.byref(params), n, src_tab, wd, wd, h, dst_tab, pitch,
+                                                              torch.cuda.current_stream().cuda_stream))
+        torch.cuda.synchronize()
+        got = np.stack([t[:, :g.out_w].cpu().numpy() for t in dst])
+    else:
+        got = prlib_amd.binarize(torch.from_numpy(np.stack(pages)).to(dev), params).cpu().numpy()
+    st = prlib_amd.last_stats()
+    assert all(got[i].shape == f.result().shape for i, f in enumerate(want))
+    b = sum(int((got[i] != f.result()).sum()) for i, f in enumerate(want))
+    bad += b
+    c = zlib.crc32(np.ascontiguousarray(got).tobytes())
+    crc = zlib.crc32(np.ascontiguousarray(got).tobytes(), crc)
+    rows.append(dict(name=name, group=group, bad=b, crc=c, pages=len(pages), pixels=int(st.pixels), sweep=int(st.exact_sweep_pages),
+                     literal=int(st.literal_pages), exact=int(st.exact_pixels), refined=int(st.refined_pixels)))
+print("MISMATCH", bad, "CRC", crc, "CASES", len(cases))
+print("STATS " + json.dumps(rows))
+'''
+_forced_results = {}
+_forced_dead = []
+
+
+def _forced_child(which, **knobs):
+    """The rows of one child of _FORCED_CHILD (each setting runs once per session): {case name: its statistics and CRC}."""
+    import json
+    import subprocess
+    import sys
+    import time
+
+    key = (which,) + tuple(sorted(knobs.items()))
+    if key in _forced_results:
+        res = _forced_results[key]
+        assert not isinstance(res, str), f"this setting failed before and is not started again: {res}"
+        return res
+    assert not _forced_dead, f"an earlier child died, nothing more is started on the GPU: {_forced_dead[0]}"
+    env = {k: v for k, v in os.environ.items() if k not in ("PRL_HIP_FORCE_EXACT", "PRL_HIP_WOLF_SIDE", "PRL_HIP_SEGMAX_CAP")}
+    env.update(knobs)
+    code = _FORCED_CHILD % dict(root=ROOT, tests=os.path.join(ROOT, "tests"))
+    t0 = time.time()
+    _forced_results[key] = f"{key}: did not finish"   # (replaced below: a setting that failed in any way is never started twice)
+    try:
+        r = subprocess.run([sys.executable, "-c", code, which], capture_output=True, text=True, timeout=120, env=env)
+    except subprocess.TimeoutExpired as e:
+        _forced_dead.append((key, "time limit", str(e.stderr or "")[-2000:]))
+        raise
+    print(f"forced-exact child {key}: {time.time() - t0:.1f} s")
+    if r.returncode != 0 or "illegal memory access" in r.stderr:   # a signal, an abort, a GPU fault or any other error: nothing more runs
+        _forced_dead.append((key, r.returncode, r.stderr[-2000:]))
+    assert r.returncode == 0, (key, r.returncode, r.stdout[-2000:] + r.stderr[-2000:])
+    assert not _forced_dead, _forced_dead[0]
+    head = [ln for ln in r.stdout.splitlines() if ln.startswith("MISMATCH")]
+    rows = [ln for ln in r.stdout.splitlines() if ln.startswith("STATS ")]
+    assert head and rows, r.stdout[-2000:] + r.stderr[-2000:]
+    rows = json.loads(rows[0][6:])
+    wrong = [x for x in rows if x["bad"]]
+    if not head[0].startswith("MISMATCH 0 ") or wrong:
+        _forced_results[key] = f"{key}: {head[0]} {wrong}"
+    assert head[0].startswith("MISMATCH 0 ") and not wrong, (key, head[0], wrong)
+    res = dict(head=head[0], rows={x["name"]: x for x in rows})
+    assert len(res["rows"]) == len(rows)
+    _forced_results[key] = res
+    return res
+
+
+def test_forced_exact_sweep_equals_the_oracle_and_the_ordinary_path(cuda_device):
+    """Every instantiation and strip kind of k_fused_exact, for all five methods: one border strip and interior + border strips at
+    w = 15 and 31, the extended last strip at w = 101, the WIDE instantiation at w = 201, the four shift classes, Feng's parameters
+    and page minimum, document / noise / flat / black / dark-corner pages (flat and black: Wolf-Jolion's degenerate coefficient
+    block, c1 = 0 and eps1 = inf - every pixel goes to the interval test), byte masks with and without the morphology pass, a large
+    radius, the page-table entry.  The same script without the knob is the control: same bytes, no page redone.
+    Ties reach the fix-up list from the exact sweep too: the flat square of a Wolf-Jolion page on its threshold (the lazy literal
+    devianceMax, entered from the redo) and Feng's rational ties (4 pages of 1536 x 1536 hold some: the control's count is
+    non-zero at that size and the forced run reports the same number - a true tie is one on either path)."""
+    forced = _forced_child("all", PRL_HIP_FORCE_EXACT="1")
+    for name, x in forced["rows"].items():
+        assert x["sweep"] == x["pages"] and x["literal"] == 0, x
+        assert x["exact"] <= x["pixels"] and x["refined"] <= x["pixels"], x
+    for morph in (0, 2):
+        assert forced["rows"][f"wolf ties m{morph}"]["exact"] >= 24 * 24 // 2, forced["rows"][f"wolf ties m{morph}"]
+    plain = _forced_child("all")
+    assert plain["head"] == forced["head"]
+    assert set(plain["rows"]) == set(forced["rows"]) and len(plain["rows"]) >= 2 * (20 + 9 + 3 + 4 + 2) + 2 + 2 + 1
+    for name, x in plain["rows"].items():
+        assert x["sweep"] == 0, x
+        assert x["crc"] == forced["rows"][name]["crc"], name
+    print("exact_pixels of the tie cases (forced / control):",
+          {n: (forced["rows"][n]["exact"], plain["rows"][n]["exact"]) for n in ("wolf ties m0", "wolf ties m2", "feng ties")})
+    assert plain["rows"]["feng ties"]["exact"] > 0
+    assert forced["rows"]["feng ties"]["exact"] == plain["rows"]["feng ties"]["exact"]
+
+
+def test_forced_exact_sweep_of_wolfjolion_on_one_stream(cuda_device):
+    """PRL_HIP_WOLF_SIDE=0: sweep B and the coefficient kernels of the redo run on the caller's stream, before the exact sweep,
+    instead of beside it with the sweep waiting for ev_coeff.  Same bytes as with the side stream."""
+    forced = _forced_child("all", PRL_HIP_FORCE_EXACT="1")
+    one = _forced_child("wolf", PRL_HIP_FORCE_EXACT="1", PRL_HIP_WOLF_SIDE="0")
+    assert len(one["rows"]) == 2 * (4 + 3 + 1 + 1) + 2
+    for name, x in one["rows"].items():
+        assert x["sweep"] == x["pages"] and x["literal"] == 0, x
+        assert x["crc"] == forced["rows"][name]["crc"], name
+    for morph in (0, 2):
+        assert one["rows"][f"wolf ties m{morph}"]["exact"] >= 24 * 24 // 2
+
+
+def test_forced_exact_sweep_of_a_wolfjolion_batch_in_page_chunks(cuda_device):
+    """64 per-wavefront maxima slots (PRL_HIP_SEGMAX_CAP): the 12 pages of 200 x 1300 go in page chunks (10 + 2), every chunk is
+    redone by the exact sweep in the workspace the chunk before it left, and the call's statistics add the chunks up."""
+    r = _forced_child("chunks", PRL_HIP_FORCE_EXACT="1", PRL_HIP_SEGMAX_CAP="64")
+    for morph in (0, 2):
+        x = r["rows"][f"chunks m{morph}"]
+        assert x["pages"] == 12 and x["sweep"] == 12 and x["literal"] == 0, x
+        assert x["pixels"] == 12 * (200 - 31) * (1300 - 31), x
+
+
+def test_product_library_ignores_force_exact(cuda_device):
+    """PRL_HIP_FORCE_EXACT belongs to the test-hooks build: libprlib_hip.so does not read it."""
+    r = _forced_child("product", PRL_HIP_FORCE_EXACT="1")
+    x = r["rows"]["product m0"]
+    assert x["sweep"] == 0 and x["literal"] == 0 and x["pages"] == 1, x

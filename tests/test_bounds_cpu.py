@@ -237,23 +237,13 @@ def test_strip_layout(prl):
     from prlib_amd import _capi
 
     SAUVOLA, NIBLACK, WOLFJOLION, NICK, FENG = range(5)
-_HOOKS = None
-
-
-def _hooks():
-    """libprlib_hip_testhooks.so: the product library exports only what include/prl_hip.h declares; the prl_hip_internal_* entries
-    (host-side helpers of the fused pipeline, no device needed) live in the test-hooks build."""
-    global _HOOKS
-    if _HOOKS is None:
-        from prlib_amd import _capi
-
-        _HOOKS = C.CDLL(_capi.HOOKS_LIB_PATH)
-    return _HOOKS
     L = _hooks()
     L.prl_hip_internal_strip_layout.argtypes = [C.c_int] * 5 + [C.POINTER(C.c_int)]
     out = (C.c_int * 2)()
+    calls = [0]   # (counted at the end: every expectation below has run)
 
     def layout(method, w, width, bit_out=0):
+        calls[0] += 1
         ow = width - 1 if method in (SAUVOLA, NIBLACK) else width - w
         n = L.prl_hip_internal_strip_layout(method, w, width, ow, bit_out, out)
         return n, out[0], out[1]
@@ -268,7 +258,8 @@ def _hooks():
     assert layout(WOLFJOLION, 21, 2480) == (6, 488, 0)
     assert layout(SAUVOLA, 41, 486) == (1, 472, 1) and layout(SAUVOLA, 41, 487) == (2, 472, 0)
     assert layout(SAUVOLA, 101, 456) == (1, 408, 1) and layout(SAUVOLA, 101, 457) == (2, 408, 0)
-    for w in (9, 15, 21, 31, 41, 51, 101, 151, 201, 257):
+    windows = (9, 15, 21, 31, 41, 51, 101, 151, 201, 257)
+    for w in windows:
         uo8, h = ((512 - (w - 1)) // 8) * 8, w // 2
         for width in range(w + 2, 2200, 3):
             ow = width - 1
@@ -283,3 +274,21 @@ def _hooks():
                 assert ow - xs <= 512 and xs + 1 - h + 504 >= width - 1
             else:
                 assert ow - (n - 1) * uo <= uo
+    assert calls[0] == 12 + sum(len(range(w + 2, 2200, 3)) for w in windows)
+
+
+def test_strip_layout_asserts_something():
+    """test_strip_layout's body: the fixed expectations and the width loop are statements of the function itself (not of a helper
+    pasted into it), and it ends on the call count."""
+    import ast
+    import inspect
+    import sys
+
+    tree = ast.parse(inspect.getsource(sys.modules[__name__]))
+    fn = [n for n in tree.body if isinstance(n, ast.FunctionDef) and n.name == "test_strip_layout"]
+    assert len(fn) == 1
+    asserts = [n for n in ast.walk(fn[0]) if isinstance(n, ast.Assert)]
+    compares = [c for a in asserts for c in ast.walk(a.test) if isinstance(c, ast.Call) and getattr(c.func, "id", "") == "layout"]
+    assert len(asserts) >= 16 and len(compares) >= 12
+    assert isinstance(fn[0].body[-1], ast.Assert) and "calls" in ast.dump(fn[0].body[-1])
+    assert sum(isinstance(n, ast.FunctionDef) and n.name == "_hooks" for n in ast.walk(tree)) == 1

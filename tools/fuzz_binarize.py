@@ -25,7 +25,12 @@ ap.add_argument("--real", type=float, default=0.0, help="probability that a page
 ap.add_argument("--adversarial", type=float, default=0.0, help="probability of a call on large pages of stripes whose levels sit inside the "
                 "float32 decision band on every second pixel (bench.adversarial_stripes; methods 0, 1, 3): the refine queue overflows, the "
                 "exact sweep redoes the pages")
+ap.add_argument("--force-exact", type=int, default=0, help="1: every page of an auto-mode call is redone by the exact sweep (k_fused_exact; "
+                "PRL_HIP_FORCE_EXACT of the test-hooks build, implies --hooks 1): the only way Wolf-Jolion and Feng pages get there")
 a = ap.parse_args()
+if a.force_exact:
+    a.hooks = 1
+    os.environ["PRL_HIP_FORCE_EXACT"] = "1"   # (knobs are read once, at the library's first call)
 if a.hooks:
     prlib_amd._capi.use_library(prlib_amd._capi.HOOKS_LIB_PATH)
 rng = np.random.default_rng(a.seed)
