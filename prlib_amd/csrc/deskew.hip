@@ -1222,8 +1222,8 @@ int deskew_pages_per_pass(int n_pages, int width, int height)
 // from the gray histogram alone (one streaming read of the pages; no mask, no lists).  The chain sizes its passes with it: the
 // search of a pass lasts as long as its heaviest page (0.6 us per point through one CU's atomic path), so a batch of photographs
 // with a dark table in them wants few large passes, text scans the usual ones.  Synchronises `hs`.
-int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                      int height, std::vector<unsigned>* points, hipStream_t hs)
+int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const PageSet& src, int width, int height,
+                      std::vector<unsigned>* points, hipStream_t hs)
 {
     points->assign((size_t)n_pages, 0u);
     const size_t gray_page = r256((size_t)width * height);
@@ -1241,11 +1241,11 @@ int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const uint8_t* 
     std::vector<int> h_thr((size_t)sub);
     for (int first = 0; first < n_pages; first += sub) {
         const int cnt = std::min(sub, n_pages - first);
-        PageSet g = pages_from(page_set(src, src_page_stride, src_step), first);
+        PageSet g = pages_from(src, first);
         if (channels != 1) {
             uint8_t* gray_ws = static_cast<uint8_t*>(ctx->ppht_buf[2]);
-            st = prl_hip_bgr2gray_batch_device(cnt, channels, src + (size_t)first * src_page_stride, src_page_stride, src_step, width, height,
-                                               gray_ws, gray_page, (size_t)width, hs);
+            st = prl_hip_bgr2gray_batch_device(cnt, channels, g.base, g.page_stride, g.step, width, height, gray_ws, gray_page,
+                                               (size_t)width, hs);
             if (st != PRL_OK) return st;
             g = page_set(gray_ws, gray_page, (size_t)width);
         }
@@ -1267,18 +1267,18 @@ int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const uint8_t* 
 }
 
 // First half of prl::deskew on `cnt` pages (cnt <= deskew_pages_per_pass): gray -> Otsu -> HoughLinesP -> angle vote.
-int deskew_find(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                int height, DeskewPlan* plan, hipStream_t hs, SearchStart* start)
+int deskew_find(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, DeskewPlan* plan, hipStream_t hs,
+                SearchStart* start)
 {
     const size_t gray_page = r256((size_t)width * height);
     std::lock_guard<std::mutex> lk(ctx->ppht_mu);
     int st;
-    PageSet g = page_set(src, src_page_stride, src_step);
+    PageSet g = src;
     if (channels != 1) {  // deskew.cpp:214-217
         st = ensure_buffer(&ctx->ppht_buf[2], &ctx->ppht_bytes[2], gray_page * (size_t)cnt);
         if (st != PRL_OK) return st;
         uint8_t* gray_ws = static_cast<uint8_t*>(ctx->ppht_buf[2]);
-        st = prl_hip_bgr2gray_batch_device(cnt, channels, src, src_page_stride, src_step, width, height, gray_ws, gray_page,
+        st = prl_hip_bgr2gray_batch_device(cnt, channels, src.base, src.page_stride, src.step, width, height, gray_ws, gray_page,
                                            (size_t)width, hs);
         if (st != PRL_OK) return st;
         g = page_set(gray_ws, gray_page, (size_t)width);
@@ -1307,8 +1307,8 @@ int deskew_find(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_
 }
 
 // Second half: rotate.
-int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, const uint8_t* src, size_t src_page_stride,
-                 size_t src_step, int width, int height, uint8_t* dst, size_t dst_page_stride, size_t dst_step, hipStream_t hs)
+int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, const PageSet& src, int width, int height,
+                 const PageSetOut& dst, hipStream_t hs)
 {
     if (plan.warp.size() != sizeof(WarpPage) * (size_t)cnt) return PRL_ERR_BAD_ARG;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -1320,20 +1320,18 @@ int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, 
     ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
     PRL_HIP_CHECK(hipMemcpyAsync(ctx->small, plan.warp.data(), plan.warp.size(), hipMemcpyHostToDevice, hs));
     PRL_HIP_CHECK(hipStreamSynchronize(hs));  // pageable source
-    const PageSet s = page_set(src, src_page_stride, src_step);
-    const PageSetOut d = page_set_out(dst, dst_page_stride, dst_step);
-    return launch_warp(channels, s, d, width, height, cnt, plan.max_ow, plan.max_oh, static_cast<const WarpPage*>(ctx->small), hs);
+    return launch_warp(channels, src, dst, width, height, cnt, plan.max_ow, plan.max_oh, static_cast<const WarpPage*>(ctx->small), hs);
 }
 
-int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                 int height, uint8_t* dst, size_t dst_page_stride, size_t dst_step, int32_t* out_wh, double* angles, hipStream_t hs)
+int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, const PageSetOut& dst,
+                 int32_t* out_wh, double* angles, hipStream_t hs)
 {
     DeskewPlan plan;
-    int st = deskew_find(ctx, cnt, channels, src, src_page_stride, src_step, width, height, &plan, hs);
+    int st = deskew_find(ctx, cnt, channels, src, width, height, &plan, hs);
     if (st != PRL_OK) return st;
     std::copy(plan.wh.begin(), plan.wh.end(), out_wh);
     if (angles) std::copy(plan.angles.begin(), plan.angles.end(), angles);
-    return deskew_apply(ctx, plan, cnt, channels, src, src_page_stride, src_step, width, height, dst, dst_page_stride, dst_step, hs);
+    return deskew_apply(ctx, plan, cnt, channels, src, width, height, dst, hs);
 }
 
 }  // namespace prl_hip
@@ -1566,11 +1564,12 @@ int prl_hip_deskew_batch_device(int n_pages, int channels, const uint8_t* d_src,
     int st = current_device(&dev);
     if (st != PRL_OK) return st;
     DeviceCtx* ctx = device_ctx(dev);
+    const PageSet src = page_set(d_src, src_page_stride, src_step);
+    const PageSetOut dst = page_set_out(d_dst, dst_page_stride, dst_step);
     const int chunk = deskew_pages_per_pass(n_pages, width, height);
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
-        st = deskew_pages(ctx, cnt, channels, d_src + (size_t)first * src_page_stride, src_page_stride, src_step, width, height,
-                          d_dst + (size_t)first * dst_page_stride, dst_page_stride, dst_step, out_wh + 2 * first,
+        st = deskew_pages(ctx, cnt, channels, pages_from(src, first), width, height, pages_from(dst, first), out_wh + 2 * first,
                           angles ? angles + first : nullptr, static_cast<hipStream_t>(stream));
         if (st != PRL_OK) return st;
     }

@@ -828,8 +828,7 @@ static int lab_tables(DeviceCtx* ctx, hipStream_t s, LabTables* lt)
     return PRL_OK;
 }
 
-static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                             int height, uint8_t* planes, hipStream_t s)
+static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const PageSet& ps, int width, int height, uint8_t* planes, hipStream_t s)
 {
     int st = device_acquire(ctx, s);
     if (st != PRL_OK) return st;
@@ -840,7 +839,6 @@ static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_
     const size_t px = (size_t)width * height;
     uint8_t* L = planes;
     uint8_t* AB = L + px * (size_t)cnt;
-    const PageSet ps = page_set(src, src_page_stride, src_step);
     const dim3 grid((width + 255) / 256, height, cnt);
     hipLaunchKernelGGL(k_lbgr2lab, grid, dim3(256), 0, s, ps, channels, width, height, lt, L, AB, px);
     PRL_HIP_CHECK(hipGetLastError());
@@ -864,8 +862,8 @@ static int nlm_locked(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, 
     return nlm_planes_locked(ctx, 1, cnt, 2, 3.0f, sab, width, height, dab, s);  // hForColorComponents = 3
 }
 
-static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, uint8_t* dst,
-                              size_t dst_page_stride, size_t dst_step, hipStream_t s)
+static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, const PageSetOut& pd,
+                              hipStream_t s)
 {
     int st = device_acquire(ctx, s);
     if (st != PRL_OK) return st;
@@ -876,37 +874,35 @@ static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8
     const size_t px = (size_t)width * height;
     const uint8_t* L2 = planes + 3 * px * (size_t)cnt;
     const uint8_t* AB2 = L2 + px * (size_t)cnt;
-    const PageSetOut pd = page_set_out(dst, dst_page_stride, dst_step);
     const dim3 grid((width + 255) / 256, height, cnt);
     hipLaunchKernelGGL(k_lab2lbgr, grid, dim3(256), 0, s, L2, AB2, px, channels, width, height, lt, pd);
     PRL_HIP_CHECK(hipGetLastError());
     return PRL_OK;
 }
 
-int denoise_convert_in(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                       int height, uint8_t* planes, hipStream_t s)
+int denoise_convert_in(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, uint8_t* planes, hipStream_t s)
 {
     std::lock_guard<std::mutex> lk(ctx->mu);
-    return convert_in_locked(ctx, cnt, channels, src, src_page_stride, src_step, width, height, planes, s);
+    return convert_in_locked(ctx, cnt, channels, src, width, height, planes, s);
 }
 int denoise_nlm(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int width, int height, hipStream_t s)
 {
     std::lock_guard<std::mutex> lk(ctx->mu);
     return nlm_locked(ctx, cnt, strength, planes, width, height, s);
 }
-int denoise_convert_out(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, uint8_t* dst,
-                        size_t dst_page_stride, size_t dst_step, hipStream_t s)
+int denoise_convert_out(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, const PageSetOut& dst,
+                        hipStream_t s)
 {
     std::lock_guard<std::mutex> lk(ctx->mu);
-    return convert_out_locked(ctx, cnt, channels, planes, width, height, dst, dst_page_stride, dst_step, s);
+    return convert_out_locked(ctx, cnt, channels, planes, width, height, dst, s);
 }
 // the whole stage on pages [0, cnt) with the planes in the shared scratch area: one lock over all three parts
-int denoise_all_locked(DeviceCtx* ctx, int cnt, int channels, float strength, const uint8_t* src, size_t src_page_stride, size_t src_step,
-                       int width, int height, uint8_t* dst, size_t dst_page_stride, size_t dst_step, uint8_t* planes, hipStream_t s)
+int denoise_all_locked(DeviceCtx* ctx, int cnt, int channels, float strength, const PageSet& src, int width, int height,
+                       const PageSetOut& dst, uint8_t* planes, hipStream_t s)
 {
-    int st = convert_in_locked(ctx, cnt, channels, src, src_page_stride, src_step, width, height, planes, s);
+    int st = convert_in_locked(ctx, cnt, channels, src, width, height, planes, s);
     if (st == PRL_OK) st = nlm_locked(ctx, cnt, strength, planes, width, height, s);
-    if (st == PRL_OK) st = convert_out_locked(ctx, cnt, channels, planes, width, height, dst, dst_page_stride, dst_step, s);
+    if (st == PRL_OK) st = convert_out_locked(ctx, cnt, channels, planes, width, height, dst, s);
     return st;
 }
 }  // namespace prl_hip
@@ -964,10 +960,12 @@ int prl_hip_denoise_batch_device(int n_pages, int channels, float strength, cons
     st = ensure_scratch(ctx, 6 * px * (size_t)chunk);
     if (st != PRL_OK) return st;
     auto* base = static_cast<uint8_t*>(ctx->scratch);
+    const PageSet src = page_set(d_src, src_page_stride, src_step);
+    const PageSetOut dst = page_set_out(d_dst, dst_page_stride, dst_step);
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
-        st = denoise_all_locked(ctx, cnt, channels, strength, d_src + (size_t)first * src_page_stride, src_page_stride, src_step, width, height,
-                                d_dst + (size_t)first * dst_page_stride, dst_page_stride, dst_step, base, static_cast<hipStream_t>(stream));
+        st = denoise_all_locked(ctx, cnt, channels, strength, pages_from(src, first), width, height, pages_from(dst, first), base,
+                                static_cast<hipStream_t>(stream));
         if (st != PRL_OK) return st;
     }
     return PRL_OK;

@@ -328,16 +328,16 @@ bool fused_supports(const ThrParams& tp);
 int fused_max_pages(const ThrParams& tp);  // pages one fused_run call can take (Wolf-Jolion: per-wavefront maxima storage)
 
 // ---- thinning (thin.hip): the C entry plus the option to thin cv::bitwise_not of the source (chain glue) ------
-int thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
-                      int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream, bool invert_input);
+// (arguments as checked by prl_hip_thin_batch_device; n_pages >= 1)
+int thin_batch_device(int method, int n_pages, const PageSet& src, int width, int height, const PageSetOut& dst, void* stream,
+                      bool invert_input);
 
 // ---- prl::denoise in three parts (nlm.hip; the chain separates its streaming parts from its compute part) ----------------
 size_t denoise_plane_bytes(int width, int height);   // per page: L, ab, L', ab'
-int denoise_convert_in(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                       int height, uint8_t* planes, hipStream_t s);
+int denoise_convert_in(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, uint8_t* planes, hipStream_t s);
 int denoise_nlm(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int width, int height, hipStream_t s);
-int denoise_convert_out(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, uint8_t* dst,
-                        size_t dst_page_stride, size_t dst_step, hipStream_t s);
+int denoise_convert_out(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, const PageSetOut& dst,
+                        hipStream_t s);
 
 // ---- deskew (deskew.hip): one pass over `cnt` pages, as its two halves (the chain overlaps them) or in one go ------
 int deskew_pages_per_pass(int n_pages, int width, int height);
@@ -363,16 +363,17 @@ struct SearchStart {
     void finish() { { std::lock_guard<std::mutex> lk(mu); done = true; } cv.notify_all(); }
     bool wait() { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return recorded || done; }); return recorded; }
 };
-int deskew_find(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                int height, DeskewPlan* plan, hipStream_t hs, SearchStart* start = nullptr);
+// (the page sets of the deskew functions are contiguous batches: base + page_stride, no pointer table)
+int deskew_find(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, DeskewPlan* plan, hipStream_t hs,
+                SearchStart* start = nullptr);
 // dark pixels (<= the page's Otsu threshold) per page = the points HoughLinesP will visit; takes ctx->ppht_mu, synchronises hs
-int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                      int height, std::vector<unsigned>* points, hipStream_t hs);
+int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const PageSet& src, int width, int height,
+                      std::vector<unsigned>* points, hipStream_t hs);
 // prl::rotate of every page by its angle (copy where none was found); takes ctx->mu
-int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, const uint8_t* src, size_t src_page_stride,
-                 size_t src_step, int width, int height, uint8_t* dst, size_t dst_page_stride, size_t dst_step, hipStream_t hs);
-int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const uint8_t* src, size_t src_page_stride, size_t src_step, int width,
-                 int height, uint8_t* dst, size_t dst_page_stride, size_t dst_step, int32_t* out_wh, double* angles, hipStream_t hs);
+int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, const PageSet& src, int width, int height,
+                 const PageSetOut& dst, hipStream_t hs);
+int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, const PageSetOut& dst,
+                 int32_t* out_wh, double* angles, hipStream_t hs);
 // ppht_group.hip: HoughLinesP's second stage with the accumulator in LDS, a group of workgroups per page.  Device pointers are
 // those of ppht_pages' workspace (deskew.hip); the host arrays must stay alive until the stream has been synchronised.
 struct PphtGroupIn {

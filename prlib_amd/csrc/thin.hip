@@ -277,26 +277,24 @@ extern "C" {
 int prl_hip_thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
                               int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    return prl_hip::thin_batch_device(method, n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride,
-                                      dst_step, stream, false);
+    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;  // "Input image for thinning is empty" (thinZhangSuen.cpp:59-62)
+    if (method != PRL_THIN_ZHANGSUEN && method != PRL_THIN_GUOHALL) return PRL_ERR_BAD_ARG;
+    if (n_pages < 0 || !d_src || !d_dst || src_step < (size_t)width || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
+    if (n_pages == 0) return PRL_OK;
+    return prl_hip::thin_batch_device(method, n_pages, page_set(d_src, src_page_stride, src_step), width, height,
+                                      page_set_out(d_dst, dst_page_stride, dst_step), stream, false);
 }
 
 }  // extern "C"
 
 namespace prl_hip {
-int thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
-                      int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream, bool invert_input)
+int thin_batch_device(int method, int n_pages, const PageSet& ps, int width, int height, const PageSetOut& pd, void* stream,
+                      bool invert_input)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;  // "Input image for thinning is empty" (thinZhangSuen.cpp:59-62)
-    if (method != PRL_THIN_ZHANGSUEN && method != PRL_THIN_GUOHALL) return PRL_ERR_BAD_ARG;
-    if (n_pages < 0 || !d_src || !d_dst || src_step < (size_t)width || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    if (n_pages == 0) return PRL_OK;
     if (n_pages > 32768) {  // the page index sits in a grid dimension limited to 65535
         for (int first = 0; first < n_pages; first += 32768) {
-            const int st2 = thin_batch_device(method, std::min(32768, n_pages - first),
-                                              d_src + (size_t)first * src_page_stride, src_page_stride, src_step, width,
-                                              height, d_dst + (size_t)first * dst_page_stride, dst_page_stride, dst_step,
-                                              stream, invert_input);
+            const int st2 = thin_batch_device(method, std::min(32768, n_pages - first), pages_from(ps, first), width, height,
+                                              pages_from(pd, first), stream, invert_input);
             if (st2 != PRL_OK) return st2;
         }
         return PRL_OK;
@@ -336,8 +334,6 @@ int thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_
     auto* act1 = act0 + act_cap;
     PRL_HIP_CHECK(hipMemsetAsync(act0, 1, act_cap, s));  // before the first pass every tile counts as changed
 
-    const PageSet ps = page_set(d_src, src_page_stride, src_step);
-    const PageSetOut pd = page_set_out(d_dst, dst_page_stride, dst_step);
     const dim3 gw((unsigned)((plane_words + 255) / 256), n_pages);  // one thread per 32-pixel word
     hipLaunchKernelGGL(k_thin_pack, gw, dim3(256), 0, s, ps, width, height, wpr, A, plane_words, invert_input ? 0xffffffffu : 0u);
     PRL_HIP_CHECK(hipGetLastError());

@@ -229,6 +229,63 @@ print("DONE")
         assert np.array_equal(z["p%d" % i], outs[i].cpu().numpy()), i
 
 
+@pytest.fixture(scope="module")
+def six_pages_one_pass(prl, oracle, cuda_device, tmp_path_factory):
+    """Six 150 x 208 x 3 pages (skews 2, 0, -3, 1, a flat page, -2) through config 5 in the default single pass, pages 0 and 1
+    compared with the composed oracle; shared by the cases of test_config5_chain_runs_of_different_size_in_every_pass."""
+    import torch
+    from prlib_amd import synth
+
+    h, w = 150, 208
+    pages = []
+    for i, skew in enumerate((2.0, 0.0, -3.0, 1.0, None, -2.0)):
+        if skew is None:
+            pages.append(np.full((h, w, 3), 228, np.uint8))
+        else:
+            pages.append(np.repeat(synth.text_page_numpy(h, w, 60 + i, skew_deg=skew, shading=0.3)[..., None], 3, axis=2))
+    batch = np.stack(pages)
+    path = tmp_path_factory.mktemp("six_pages") / "in.npy"
+    np.save(path, batch)
+    outs, angles = prl.process_pages(torch.from_numpy(batch).to(cuda_device), 3, prl.SAUVOLA, 31, 0.34, 0,
+                                     denoise_strength=10.0, thin=0, deskew=True, background_normalization=True)
+    outs = [o.cpu().numpy() for o in outs]
+    for i in (0, 1):
+        want, ang = _oracle_chain5(oracle, batch[i], 3, 31, 0.34, 0, 10.0, 0)
+        assert angles[i] == ang and outs[i].shape == want.shape and np.array_equal(outs[i], want), i
+    return path, outs, np.asarray(angles)
+
+
+@pytest.mark.parametrize("overlap", ["2", "1", "0"])
+def test_config5_chain_runs_of_different_size_in_every_pass(six_pages_one_pass, tmp_path, overlap):
+    """PRL_HIP_CHAIN_PASS=3 cuts six pages into two passes of three, each with rotated (208 x 208) and unrotated (150 x 208)
+    runs, and the second search runs beside the first pass's body (overlap 2), beside all of its stages (1) or after it (0):
+    the smallest batch that walks the run split, both pass bodies and the hand-over of the pass size.  Angles, result sizes
+    and every byte must equal the default one-pass call."""
+    import subprocess
+    import sys
+
+    path, outs, angles = six_pages_one_pass
+    code = r'''
+import numpy as np, torch, sys
+sys.path.insert(0, %r)
+import prlib_amd
+prlib_amd._capi.use_library(prlib_amd._capi.HOOKS_LIB_PATH)   # the build that reads the PRL_HIP_* tuning knobs
+batch = np.load(%r)
+outs, angles = prlib_amd.process_pages(torch.from_numpy(batch).cuda(), 3, prlib_amd.SAUVOLA, 31, 0.34, 0,
+                                       denoise_strength=10.0, thin=0, deskew=True, background_normalization=True)
+np.savez(%r, angles=np.asarray(angles), **{"p%%d" %% i: o.cpu().numpy() for i, o in enumerate(outs)})
+print("DONE")
+''' % (ROOT, str(path), str(tmp_path / "out.npz"))
+    env = dict(os.environ, PRL_HIP_CHAIN_PASS="3", PRL_HIP_CHAIN_OVERLAP=overlap)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "DONE" in r.stdout, r.stdout + r.stderr
+    z = np.load(tmp_path / "out.npz")
+    assert np.array_equal(z["angles"], angles)
+    assert len({o.shape for o in outs[:3]}) == 2 and len({o.shape for o in outs[3:]}) == 2   # both passes have two run sizes
+    for i in range(len(outs)):
+        assert z["p%d" % i].shape == outs[i].shape and np.array_equal(z["p%d" % i], outs[i]), i
+
+
 def test_tail_aware_passes_give_the_same_pages(prl, cuda_device):
     """More pages than one default pass (192 with denoise) and one page that is almost all ink: the chain's census of the dark
     pixels finds that the other pages' search hides behind that page's, and runs the batch as one large pass instead of

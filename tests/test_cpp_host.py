@@ -72,6 +72,15 @@ def test_work_pool_many_callers():
     assert r.returncode == 0 and "work_pool: OK" in r.stdout, r.stdout + r.stderr
 
 
+def test_chain_schedule():
+    """prlib_amd/csrc/chain_schedule.h (the pass-size policy of the config-5 chain: starting sizes, tail-bound batches, the
+    no-tiny-last-pass rule, the NL-means balance controller, the choice of the searching kernel) against sizes worked out by
+    hand (plain C++, no device)."""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "test_chain_schedule"], check=True)
+    r = subprocess.run([os.path.join(os.path.join(ROOT, "tests", "cpp"), "test_chain_schedule")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "chain_schedule: OK" in r.stdout, r.stdout + r.stderr
+
+
 def test_cpp_boundary_compiles_against_opencv_signatures():
     """The OpenCV-present branch of the C++ boundary (prl.h: PRL_HAVE_OPENCV).  No box of this pool has OpenCV, so that
     branch is compiled - syntax only - against tests/cpp/opencv_api/: declaration-only headers carrying OpenCV's real
