@@ -425,6 +425,27 @@ int prl_hip_correct_nuil_batch_device(int n_pages, int channels, int size, const
 int prl_hip_correct_nuil_host(int channels, int size, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
                               size_t dst_step);
 
+/* ---- prl::removeLines --------------------------------------------------------------------------------------------------- */
+
+/*
+ * prl::removeLines(in, out) (src/removeLines.cpp:30-76) on 8-bit pages of 1 or 3 (BGR) channels in device memory; the result
+ * is one channel at the input's size.  gray = the 14-bit luma for 3 channels, else the page; t = getThreshVal_Otsu_8u(255 -
+ * gray) (the float64 scan, per page, on the device); bw = 255 - gray > t; horizontal = dilate(erode(bw)) with a
+ * (width / 50) x 1 rectangle, vertical the same with 1 x (height / 50), both with the offsets -k/2 .. k-1-k/2 and taps outside
+ * the page ignored; dst = 0 where bw is set and neither opening is, else 255.  Exact.  The mask and the openings run on bit
+ * planes in the device's cached scratch (3/8 byte per pixel and page, plus one gray byte for 3 channels); element lengths are
+ * not limited (width, height <= 32768 gives at most 655).  d_src == d_dst with the same strides (in place) is allowed for
+ * 1-channel pages; any other overlap returns PRL_ERR_BAD_ARG, and d_src is otherwise never written.  Enqueues on `stream`, no
+ * synchronisation.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_CHANNELS (channels
+ * other than 1 and 3: cv::threshold's Otsu takes 8UC1 only); PRL_ERR_BAD_ARG (width or height below 50: an element of size 0,
+ * cv::getStructuringElement's assertion; null pointer, negative n_pages, step < row bytes, width or height above the limit,
+ * overlapping source and destination).
+ */
+int prl_hip_remove_lines_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                      int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_remove_lines_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

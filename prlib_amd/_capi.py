@@ -56,6 +56,7 @@ EXPORTED_SYMBOLS = [
     "prl_hip_adaptive_threshold_batch_device", "prl_hip_adaptive_threshold_host", "prl_hip_default_adaptive_params",
     "prl_hip_binarize_adaptive_batch_device", "prl_hip_binarize_adaptive_host",
     "prl_hip_morphology_batch_device", "prl_hip_morphology_host", "prl_hip_correct_nuil_batch_device", "prl_hip_correct_nuil_host",
+    "prl_hip_remove_lines_batch_device", "prl_hip_remove_lines_host",
 ]
 
 
@@ -195,6 +196,8 @@ def lib() -> C.CDLL:
         L.prl_hip_morphology_host.argtypes = [i, i, i, i, i, vp, sz, i, i, vp, sz]
         L.prl_hip_correct_nuil_batch_device.argtypes = [i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_correct_nuil_host.argtypes = [i, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_remove_lines_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_remove_lines_host.argtypes = [i, vp, sz, i, i, vp, sz]
         _lib = L
     return _lib
 

@@ -548,6 +548,13 @@ int gm_host(int channels, int op, int shape, int kw, int kh, bool nuil, const ui
 
 }  // namespace
 
+int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
+                         hipStream_t stream)
+{
+    const GmPlan plan = gm_plan(PRL_MORPH_OPEN, PRL_SHAPE_RECT, kw, kh, false, false, false);
+    return gm_run(plan, width, height, 1, false, src, dst, n_pages, tmp, nullptr, stream);
+}
+
 }  // namespace prl_hip
 
 using namespace prl_hip;

@@ -14,6 +14,7 @@
 //   src/binarizations/binarizeAT.h:33, binarizeAGT.h:32    prl::binarizeAT, prl::binarizeAGT
 //   src/binarizations/binarizePureAdaptiveGaussian.h:33    prl::binarizePureAdaptiveGaussian
 //   src/correctNUIL.h:32                                   prl::correctNUIL
+//   src/removeLines.h:38                                   prl::removeLines
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -102,6 +103,15 @@ CV_EXPORTS void binarizePureAdaptiveGaussian(const cv::Mat& inputImage, cv::Mat&
 // size above 255 (OpenCV has no upper limit: not here).  The output is a new continuous Mat of the input's size and type; the
 // input's pixels are never written (out may be in, or a view of it).
 CV_EXPORTS void correctNUIL(const cv::Mat& inputImage, cv::Mat& outputImage, int structuringElementSize = 31);
+
+// src/removeLines.h:38 - strips ruled lines, table grids and form boxes (removeLines.cpp:30-76): [BGR -> gray],
+// bw = cv::threshold(~gray, THRESH_BINARY | THRESH_OTSU), horizontal / vertical = cv::erode then cv::dilate of bw with
+// getStructuringElement(MORPH_RECT, Size(cols / 50, 1)) / Size(1, rows / 50), out = ~((bw - horizontal) - vertical): 8UC1 at the
+// input's size.  cv::Exception: StsAssert for an empty input and for cols < 50 or rows < 50 (getStructuringElement's size 0);
+// StsUnsupportedFormat for channel counts other than 1 and 3 (cv::threshold's Otsu takes 8UC1 only) and for a depth other than
+// CV_8U.  On every error outputImage stays untouched.  The output is a new continuous Mat; the input's pixels are never
+// written (out may be in, or a view of it).
+CV_EXPORTS void removeLines(const cv::Mat& inputImage, cv::Mat& outputImage);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

@@ -200,6 +200,22 @@ void prl::correctNUIL(const cv::Mat& inputImage, cv::Mat& outputImage, int struc
     outputImage = result;
 }
 
+// removeLines.cpp:30-76.  The reference's order: cvtColor for 3 channels, cv::threshold (8UC1 only: its assertions cover the
+// empty Mat, the other channel counts and depths), then getStructuringElement's assertion on a size of 0.
+void prl::removeLines(const cv::Mat& inputImage, cv::Mat& outputImage)
+{
+    if (inputImage.empty()) PRL_FAIL_CV(cv::Error::StsAssert, "!_src.empty()");                      // [upstream] cv::threshold
+    if (inputImage.depth() != CV_8U || (inputImage.channels() != 1 && inputImage.channels() != 3))
+        PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::removeLines: 8-bit images of 1 or 3 channels only");
+    if (inputImage.cols < 50 || inputImage.rows < 50)
+        PRL_FAIL_CV(cv::Error::StsAssert, "ksize.width > 0 && ksize.height > 0");                   // [upstream] normalizeAnchor
+    cv::Mat result(inputImage.rows, inputImage.cols, CV_8UC1);
+    const int st = prl_hip_remove_lines_host(inputImage.channels(), inputImage.data, inputImage.step, inputImage.cols,
+                                             inputImage.rows, result.data, result.step);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
 namespace {
 
 constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255

@@ -130,6 +130,7 @@ struct EnvKnobs {
     int literal_mode = 0;         // PRL_HIP_MODE=literal
     bool median_generic = false;  // PRL_HIP_MEDIAN_GENERIC=1  the histogram kernel for every window (median.hip), k = 3 and 5 included
     bool gmorph_literal = false;  // PRL_HIP_GMORPH_LITERAL=1  the by-the-definition kernel for every element (gmorph.hip)
+    bool lines_bytes = false;     // PRL_HIP_LINES_BYTES=1     removeLines' openings on byte masks through k_gm_span (lines.hip)
 };
 const EnvKnobs& env_knobs();
 
@@ -401,6 +402,11 @@ void host_slots_free(DeviceCtx* ctx);  // host_batch.hip: the pinned bounce slot
 // ---- median (median.hip): one cv::medianBlur pass, odd ksize >= 3, source and destination distinct; enqueues only ----------
 int median_pass_pages(int width, int height, int channels, int ksize, const PageSet& src, const PageSetOut& dst, int n_pages,
                       hipStream_t stream);
+
+// ---- flat-element morphology (gmorph.hip): OPEN with a kw x kh rectangle (1..255 each way) on 1-channel pages of a contiguous
+// batch, source and destination distinct; `tmp`: n_pages * width * height bytes; enqueues only (caller holds ctx->mu) ----------
+int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
+                         hipStream_t stream);
 
 // ---- morphology (morph.hip) ------------------------------------------------------------------
 int morph_run(int iterations, const PageSet& src, int n_pages, int width, int height,
