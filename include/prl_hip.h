@@ -446,6 +446,102 @@ int prl_hip_remove_lines_batch_device(int n_pages, int channels, const uint8_t* 
                                       int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
 int prl_hip_remove_lines_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
 
+/* ---- tone: histogram, table look-up, prl::gammaCorrection, the white balances, prl::cleanBackgroundToWhite -------------- */
+
+/*
+ * Point operations on 8-bit pages in device memory whose table depends on page statistics (tone.hip).  Every output byte of
+ * the four reference functions below is a function of the input byte and of the page's per-channel histograms only, so each
+ * runs as histogram -> 256-entry table per (page, channel) -> dst = table[src], and is exact also where the reference computes
+ * in float or double per pixel.  Pages hold `channels` interleaved bytes per pixel; pages and rows may be strided.
+ *
+ * Every entry checks in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_CHANNELS
+ * (channels outside 1..4 for the two primitives and for gamma, other than 1, 3, 4 for clean-background; the white balances take
+ * 3-channel pages and have no channel argument); PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row bytes, width or
+ * height above 32768, overlapping source and destination).  d_src == d_dst with the same strides (in place) is allowed where the
+ * result has as many channels as the source; any other overlap is PRL_ERR_BAD_ARG.  The *_batch_device entries enqueue on
+ * `stream` and do not synchronise, except where stated; the *_host entries take one page in host memory.
+ */
+
+/* d_hist[page][channel][256] = the number of pixels of the page with that value in that channel; the call overwrites it. */
+int prl_hip_histogram_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                   int height, uint32_t* d_hist, void* stream);
+
+/*
+ * cv::LUT: dst(y, x, c) = d_lut[c * 256 + src(y, x, c)].  d_lut holds [channel][256] bytes in device memory; page i reads its
+ * tables lut_page_stride bytes after page i - 1's, and a lut_page_stride of 0 gives every page the same set.
+ */
+int prl_hip_lut_batch_device(int n_pages, int channels, const uint8_t* d_lut, size_t lut_page_stride, const uint8_t* d_src,
+                             size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                             size_t dst_step, void* stream);
+
+/*
+ * prl::gammaCorrection(in, out, k, gamma) (src/balance/gammaCorrection.cpp:52-106).  g[v] = sat_u8(pow(v / 255.0, gamma) * 255.0)
+ * in double with the host's pow, then, unless |k - 1| <= 1e-7, t[v] = sat_u8((float)g[v] * (float)k) (Mat *= k on 8U is
+ * convertTo(8U, k), float32 [upstream]); sat_u8 rounds half to even and clamps, and NaN, +-inf and what lies outside int32 give 0
+ * (SURVEY.md A.6).  1, 2 or 3 channels come back with as many.  4 channels: the reference converts BGRA to BGR and its switch has
+ * no case for 4, so the result has 3 channels, the alpha byte dropped and only the k step applied; reproduced.  The table is built
+ * on the host and handed to the kernel by value.
+ */
+int prl_hip_gamma_correction_batch_device(int n_pages, int channels, double k, double gamma, const uint8_t* d_src, size_t src_page_stride,
+                                          size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                                          size_t dst_step, void* stream);
+int prl_hip_gamma_correction_host(int channels, double k, double gamma, const uint8_t* src, size_t src_step, int width, int height,
+                                  uint8_t* dst, size_t dst_step);
+
+/*
+ * prl::simpleWhiteBalance(in, out, k) (src/balance/balanceSimpleWhite.cpp:33-142) on 3-channel pages.  Per channel: the cumulative
+ * histogram as int; vmin = the first v with cum[v] >= k * total (a double product); vmax scans down from 255 while cum[vmax] >
+ * (1 - k) * total, then + 1 if below 254; scale = 255.0f / (vmax - vmin); out = (uchar)((clamp(v, vmin, vmax) - vmin) * scale),
+ * int times float, truncated.  Where the reference's behaviour is undefined: both scans stop at the array's ends (the reference
+ * reads outside its histogram for an all-zero channel and for k > 1), and a channel with vmax == vmin (0 * inf) comes out 0, which
+ * is what the x86 conversion gives.  A NaN or negative k gives the identity, by the literal comparisons.  Histograms and tables
+ * stay on the device.
+ */
+int prl_hip_simple_white_balance_batch_device(int n_pages, double k, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                              int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                              void* stream);
+int prl_hip_simple_white_balance_host(double k, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
+                                      size_t dst_step);
+
+/*
+ * prl::grayWorldWhiteBalance(in, out, pNorm, withMax) (src/balance/balanceGrayWorldWhite.cpp:37-115) on 3-channel pages.
+ * S_c = sum over v = 0..255, ascending, of (double)hist[v] * pow((double)v, p) (empty bins add nothing); m_c = pow(S_c / (cols *
+ * rows), 1 / p); r = (m1 + m2 + m0) / 3.0, or std::max(m1, std::max(m2, m0)) with with_max; out = (uchar)std::min(255.0, v * (r /
+ * m_c)), so an all-zero channel (a NaN) comes out all 255.  The reference sums pow(v, p) in raster order: for p = 1, 2, 3 every
+ * term and partial sum is an exact integer and the sum over the bins equals it bit for bit; for other p the means can differ in
+ * their last bits, and an output byte only where v * ratio lies that close to an integer.  p_norm == 1.0 runs on the device without
+ * synchronising (pow(x, 1) is skipped).  Any other p_norm needs the host's pow: the histograms are copied to the host, the tables
+ * built there (prl_hip_gray_world_luts) and copied back - that path SYNCHRONISES `stream`.
+ */
+int prl_hip_gray_world_batch_device(int n_pages, double p_norm, int with_max, const uint8_t* d_src, size_t src_page_stride,
+                                    size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                    void* stream);
+int prl_hip_gray_world_host(double p_norm, int with_max, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
+                            size_t dst_step);
+
+/*
+ * prl::cleanBackgroundToWhite(in, out) (src/cleanBackgroundToWhite.cpp:39-64) = pixCleanBackgroundToWhite(pixs, NULL, NULL, 1.0, 70,
+ * 170) [upstream]: pixBackgroundNormSimple (exactly prl_hip_bgnorm_*: 1 channel -> 1, 3 or 4 -> 3) followed by pixGammaTRC(1.0, 70,
+ * 170) in place, the table of prl_hip_clean_background_lut.  A page that the normalisation copies gets the table applied to the
+ * copy.  Uses the device's cached scratch like prl_hip_bgnorm_batch_device.
+ */
+int prl_hip_clean_background_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                          int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_clean_background_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
+                                  size_t dst_step);
+
+/*
+ * The tables themselves, built on the host: no device is needed.  The kernel that derives the white-balance tables on the device
+ * runs the same code.  prl_hip_clean_background_lut: numaGammaTRC(1.0, 70, 170) [upstream]: 0 below 70, 255 above 170, else
+ * (int)(255. * x + 0.5) with x = (float)(i - 70) / (float)100.  The two *_luts take hist[channel][256] of one 3-channel page (the
+ * layout of prl_hip_histogram_batch_device) and write luts[channel][256]; cols * rows is the sum of a channel's bins:
+ * PRL_ERR_EMPTY where it is 0, PRL_ERR_BAD_ARG where the three channels' sums differ or exceed 32768 * 32768, and for a null pointer.
+ */
+int prl_hip_gamma_lut(double k, double gamma, uint8_t lut[256]);
+int prl_hip_clean_background_lut(uint8_t lut[256]);
+int prl_hip_simple_white_balance_luts(double k, const uint32_t hist[3 * 256], uint8_t luts[3 * 256]);
+int prl_hip_gray_world_luts(double p_norm, int with_max, const uint32_t hist[3 * 256], uint8_t luts[3 * 256]);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

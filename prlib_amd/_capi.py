@@ -57,6 +57,12 @@ EXPORTED_SYMBOLS = [
     "prl_hip_binarize_adaptive_batch_device", "prl_hip_binarize_adaptive_host",
     "prl_hip_morphology_batch_device", "prl_hip_morphology_host", "prl_hip_correct_nuil_batch_device", "prl_hip_correct_nuil_host",
     "prl_hip_remove_lines_batch_device", "prl_hip_remove_lines_host",
+    "prl_hip_histogram_batch_device", "prl_hip_lut_batch_device",
+    "prl_hip_gamma_correction_batch_device", "prl_hip_gamma_correction_host",
+    "prl_hip_simple_white_balance_batch_device", "prl_hip_simple_white_balance_host",
+    "prl_hip_gray_world_batch_device", "prl_hip_gray_world_host",
+    "prl_hip_clean_background_batch_device", "prl_hip_clean_background_host",
+    "prl_hip_gamma_lut", "prl_hip_clean_background_lut", "prl_hip_simple_white_balance_luts", "prl_hip_gray_world_luts",
 ]
 
 
@@ -198,6 +204,20 @@ def lib() -> C.CDLL:
         L.prl_hip_correct_nuil_host.argtypes = [i, i, vp, sz, i, i, vp, sz]
         L.prl_hip_remove_lines_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_remove_lines_host.argtypes = [i, vp, sz, i, i, vp, sz]
+        L.prl_hip_histogram_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, vp]
+        L.prl_hip_lut_batch_device.argtypes = [i, i, vp, sz, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_gamma_correction_batch_device.argtypes = [i, i, d, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_gamma_correction_host.argtypes = [i, d, d, vp, sz, i, i, vp, sz]
+        L.prl_hip_simple_white_balance_batch_device.argtypes = [i, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_simple_white_balance_host.argtypes = [d, vp, sz, i, i, vp, sz]
+        L.prl_hip_gray_world_batch_device.argtypes = [i, d, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_gray_world_host.argtypes = [d, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_clean_background_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_clean_background_host.argtypes = [i, vp, sz, i, i, vp, sz]
+        L.prl_hip_gamma_lut.argtypes = [d, d, vp]
+        L.prl_hip_clean_background_lut.argtypes = [vp]
+        L.prl_hip_simple_white_balance_luts.argtypes = [d, vp, vp]
+        L.prl_hip_gray_world_luts.argtypes = [d, i, vp, vp]
         _lib = L
     return _lib
 

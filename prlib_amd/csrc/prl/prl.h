@@ -15,6 +15,10 @@
 //   src/binarizations/binarizePureAdaptiveGaussian.h:33    prl::binarizePureAdaptiveGaussian
 //   src/correctNUIL.h:32                                   prl::correctNUIL
 //   src/removeLines.h:38                                   prl::removeLines
+//   src/balance/gammaCorrection.h:33                       prl::gammaCorrection
+//   src/balance/balanceSimpleWhite.h:33                    prl::simpleWhiteBalance
+//   src/balance/balanceGrayWorldWhite.h:33                 prl::grayWorldWhiteBalance
+//   src/cleanBackgroundToWhite.h:40                        prl::cleanBackgroundToWhite
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -112,6 +116,19 @@ CV_EXPORTS void correctNUIL(const cv::Mat& inputImage, cv::Mat& outputImage, int
 // CV_8U.  On every error outputImage stays untouched.  The output is a new continuous Mat; the input's pixels are never
 // written (out may be in, or a view of it).
 CV_EXPORTS void removeLines(const cv::Mat& inputImage, cv::Mat& outputImage);
+
+// src/balance/gammaCorrection.h:33, balanceSimpleWhite.h:33, balanceGrayWorldWhite.h:33, src/cleanBackgroundToWhite.h:40 - point
+// operations whose table depends on page statistics (tone.hip; the arithmetic is stated in prl_hip.h).  No default arguments,
+// as in the reference.  std::invalid_argument with the reference's messages for an empty input and, for the two white
+// balances, for a channel count other than 3; cv::Exception StsUnsupportedFormat for a depth other than CV_8U and for channel
+// counts the conversion rejects (gammaCorrection: above 4; cleanBackgroundToWhite: other than 1, 3, 4: "Cannot convert RAW image
+// to Pix", formatConvert.cpp:103-104).  gammaCorrection of a 4-channel Mat returns 3 channels with only the k step applied
+// (gammaCorrection.cpp:74-97: BGRA -> BGR, and the switch has no case for 4); cleanBackgroundToWhite returns 3 channels for 3 and 4.
+// On every error outputImage stays untouched.  The output is a new continuous Mat; the input's pixels are never written.
+CV_EXPORTS void gammaCorrection(const cv::Mat& inputImage, cv::Mat& outputImage, const double k, const double gamma);
+CV_EXPORTS void simpleWhiteBalance(const cv::Mat& inputImage, cv::Mat& outputImage, const double k);
+CV_EXPORTS void grayWorldWhiteBalance(const cv::Mat& inputImage, cv::Mat& outputImage, const double pNorm, const bool withMax);
+CV_EXPORTS void cleanBackgroundToWhite(const cv::Mat& inputImage, cv::Mat& outputImage);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

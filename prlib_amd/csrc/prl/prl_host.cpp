@@ -216,6 +216,64 @@ void prl::removeLines(const cv::Mat& inputImage, cv::Mat& outputImage)
     outputImage = result;
 }
 
+// gammaCorrection.cpp:52-106.  4 channels: cvtColor(BGRA2BGR), then the switch has no case for 4 - three channels come back
+// with only the k step applied (prl_hip_gamma_correction_host reproduces it).
+void prl::gammaCorrection(const cv::Mat& inputImage, cv::Mat& outputImage, const double k, const double gamma)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Invalid parameter for GammaCorrectionFilter_OpenCV");
+    if (inputImage.depth() != CV_8U)
+        PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::gammaCorrection: 8-bit images only");        // documented deviation
+    const int cn = inputImage.channels();
+    if (cn > 4) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::gammaCorrection: 8-bit images of 1..4 channels only");
+    cv::Mat result(inputImage.rows, inputImage.cols, CV_MAKETYPE(CV_8U, cn == 4 ? 3 : cn));
+    const int st = prl_hip_gamma_correction_host(cn, k, gamma, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows,
+                                                 result.data, result.step);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
+// balanceSimpleWhite.cpp:33-142
+void prl::simpleWhiteBalance(const cv::Mat& inputImage, cv::Mat& outputImage, const double k)
+{
+    if (inputImage.empty()) throw std::invalid_argument("SimpleWhiteBalance: input image is empty.");
+    if (inputImage.channels() != 3) throw std::invalid_argument("SimpleWhiteBalance: input image hasn't 3 channels.");
+    if (inputImage.depth() != CV_8U)
+        PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::simpleWhiteBalance: 8-bit images only");     // documented deviation
+    cv::Mat result(inputImage.rows, inputImage.cols, CV_8UC3);
+    const int st = prl_hip_simple_white_balance_host(k, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows, result.data,
+                                                     result.step);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
+// balanceGrayWorldWhite.cpp:58-115
+void prl::grayWorldWhiteBalance(const cv::Mat& inputImage, cv::Mat& outputImage, const double pNorm, const bool withMax)
+{
+    if (inputImage.empty()) throw std::invalid_argument("GrayWorldWhiteBalance: input image is empty");
+    if (inputImage.channels() != 3) throw std::invalid_argument("GrayWorldWhiteBalance: input image hasn't 3 channels");
+    if (inputImage.depth() != CV_8U)
+        PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::grayWorldWhiteBalance: 8-bit images only");  // documented deviation
+    cv::Mat result(inputImage.rows, inputImage.cols, CV_8UC3);
+    const int st = prl_hip_gray_world_host(pNorm, withMax ? 1 : 0, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows,
+                                           result.data, result.step);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
+// cleanBackgroundToWhite.cpp:39-64: the converters and channel rules of prl::backgroundNormalization
+void prl::cleanBackgroundToWhite(const cv::Mat& inputImage, cv::Mat& outputImage)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image for flipping is empty");   // cleanBackgroundToWhite.cpp:43-46
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "Cannot convert RAW image to Pix\n");   // formatConvert.cpp:103-104
+    const int cn = inputImage.channels();
+    if (cn != 1 && cn != 3 && cn != 4) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "Cannot convert RAW image to Pix\n");
+    cv::Mat result(inputImage.rows, inputImage.cols, cn == 1 ? CV_8UC1 : CV_8UC3);
+    const int st = prl_hip_clean_background_host(cn, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows, result.data,
+                                                 result.step);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
 namespace {
 
 constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255
