@@ -542,6 +542,60 @@ int prl_hip_clean_background_lut(uint8_t lut[256]);
 int prl_hip_simple_white_balance_luts(double k, const uint32_t hist[3 * 256], uint8_t luts[3 * 256]);
 int prl_hip_gray_world_luts(double p_norm, int with_max, const uint32_t hist[3 * 256], uint8_t luts[3 * 256]);
 
+/* ---- prl::binarizeMokji and the grey-level co-occurrence matrix ------------------------------------------------------------ */
+
+/*
+ * prl::binarizeMokji(in, out, maxEdgeWidth = 3, minEdgeMagnitude = 20) (src/binarizations/binarizeMokji.cpp:35-94; Mokji & Abu-Bakar
+ * 2007) on 8-bit pages of 1, 3 (BGR) or 4 (BGRA) channels in device memory; the result is one channel at the input's size.  Write E
+ * for max_edge_width and M for min_edge_magnitude.
+ *   gray = the 14-bit luma for 3 / 4 channels, else the page;  dil = cv::dilate(gray, RECT (2E + 1) x (2E + 1)), anchor at the
+ *   centre, taps outside the page ignored;  matrix[dil(y, x)][gray(y, x)] += 1 over y in [E, height - E), x in [E, width - E), from
+ *   zeros (the reference never initialises its matrix: zeros are the only defined reading);  nom = sum of (m + n) matrix[n][m] and
+ *   den = sum of matrix[n][m] over the pairs with n - m >= M;  t = (int)(0.5 * nom / den + 0.5) in double, which equals
+ *   (nom + den) / (2 den) in integers for every matrix a page can give (nom < 2^53);  dst = gray > t ? 255 : 0.
+ * Exact.  Where the reference is undefined: den == 0 (an empty interior: width <= 2E or height <= 2E; no pair with n - m >= M)
+ * makes it convert a NaN to int, which on x86 is INT_MIN, and cv::threshold with a negative threshold sets every pixel: the page
+ * comes out all 255 and the threshold is reported as -1.  M >= 256 (the reference wraps 256 - M and reads outside its matrix) is
+ * "no pair", the same.  Limit: the dilation's element is at most 255 wide, so E <= 127 unless the interior is empty.
+ * The gray and dilated planes, the dilation's intermediate plane and one 256 x 256 uint32 matrix per page live in the device's
+ * cached scratch; the threshold stays on the device.  d_src == d_dst with the same strides (in place) is allowed for 1-channel
+ * pages; any other overlap returns PRL_ERR_BAD_ARG, and d_src is otherwise never written.  width, height <= 32768.  Enqueues on
+ * `stream`, no synchronisation.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_ARG (max_edge_width < 1,
+ * min_edge_magnitude < 1, max_edge_width > 127 with a non-empty interior); PRL_ERR_BAD_CHANNELS (channels other than 1, 3, 4);
+ * PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row bytes, width or height above the limit, overlapping source and
+ * destination).
+ */
+int prl_hip_binarize_mokji_batch_device(int n_pages, int channels, int max_edge_width, int min_edge_magnitude, const uint8_t* d_src,
+                                        size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                        size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_binarize_mokji_host(int channels, int max_edge_width, int min_edge_magnitude, const uint8_t* src, size_t src_step, int width,
+                                int height, uint8_t* dst, size_t dst_step);
+
+/* The threshold alone: d_thresholds[page] = t as above, -1 where den == 0.  Same source arguments, checks and workspace. */
+int prl_hip_mokji_thresholds_batch_device(int n_pages, int channels, int max_edge_width, int min_edge_magnitude, const uint8_t* d_src,
+                                          size_t src_page_stride, size_t src_step, int width, int height, int32_t* d_thresholds,
+                                          void* stream);
+
+/*
+ * The co-occurrence matrix of two 1-channel planes a and b of the same size: d_cooc[page][b(y, x)][a(y, x)] = the number of pixels
+ * of the interior y in [border, height - border), x in [border, width - border) with that pair of values, for the pairs with
+ * b - a >= min_diff; every other bin is 0.  min_diff == 0 counts every pair, those with b < a included (the square matrix is the
+ * contract); min_diff == 256 counts none.  d_cooc holds 256 * 256 uint32 per page; the call overwrites it.  An empty interior gives
+ * zeros.  Checked in this order: PRL_ERR_EMPTY; PRL_ERR_BAD_ARG (border < 0, min_diff outside 0..256); PRL_ERR_BAD_ARG (null
+ * pointer, negative n_pages, step < width, width or height above 32768).  Enqueues on `stream`, no synchronisation, no workspace.
+ */
+int prl_hip_cooccurrence_batch_device(int n_pages, int border, int min_diff, const uint8_t* d_a, size_t a_page_stride, size_t a_step,
+                                      const uint8_t* d_b, size_t b_page_stride, size_t b_step, int width, int height, uint32_t* d_cooc,
+                                      void* stream);
+
+/*
+ * Step 6 on the host, no device needed: *threshold = (nom + den) / (2 den) over the pairs n - m >= min_edge_magnitude of
+ * cooc[n * 256 + m], or -1 where den == 0 (min_edge_magnitude >= 256 included); the kernel runs the same inline code.
+ * PRL_ERR_BAD_ARG for a null pointer or min_edge_magnitude < 1.
+ */
+int prl_hip_mokji_threshold(const uint32_t cooc[256 * 256], int min_edge_magnitude, int* threshold);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

@@ -10,6 +10,7 @@ from .adaptive import adaptiveThreshold, binarizeAGT, binarizeAT, binarizeNative
 from .morphology import correctNUIL, morphologyEx  # noqa: F401
 from .lines import removeLines  # noqa: F401
 from .tone import cleanBackgroundToWhite, gammaCorrection, grayWorldWhiteBalance, histogram, lut, simpleWhiteBalance  # noqa: F401
+from .mokji import binarizeMokji, cooccurrence, mokjiThreshold, mokjiThresholds  # noqa: F401
 from .thinning import thinGuoHall, thinZhangSuen  # noqa: F401
 from .background import backgroundNormalization  # noqa: F401
 from .deskew import deskew, deskew_stats, find_angle as findAngle, find_orientation as findOrientation, houghp, rotate  # noqa: F401
@@ -23,6 +24,6 @@ from .binarizations import (  # noqa: F401
 __all__ = [
     "binarize", "binarizeSauvola", "binarizeNiblack", "binarizeWolfJolion", "binarizeNICK", "binarizeFeng", "binarizeByLocalVariances", "binarizeByLocalVariancesWithoutFilters",
     "adaptiveThreshold", "binarizeNativeAdaptive", "binarizeAT", "binarizeAGT", "binarizePureAdaptiveGaussian",
-    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
+    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
     "SAUVOLA", "NIBLACK", "WOLFJOLION", "NICK", "FENG",
 ]

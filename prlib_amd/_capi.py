@@ -63,6 +63,8 @@ EXPORTED_SYMBOLS = [
     "prl_hip_gray_world_batch_device", "prl_hip_gray_world_host",
     "prl_hip_clean_background_batch_device", "prl_hip_clean_background_host",
     "prl_hip_gamma_lut", "prl_hip_clean_background_lut", "prl_hip_simple_white_balance_luts", "prl_hip_gray_world_luts",
+    "prl_hip_binarize_mokji_batch_device", "prl_hip_binarize_mokji_host", "prl_hip_mokji_thresholds_batch_device",
+    "prl_hip_cooccurrence_batch_device", "prl_hip_mokji_threshold",
 ]
 
 
@@ -218,6 +220,11 @@ def lib() -> C.CDLL:
         L.prl_hip_clean_background_lut.argtypes = [vp]
         L.prl_hip_simple_white_balance_luts.argtypes = [d, vp, vp]
         L.prl_hip_gray_world_luts.argtypes = [d, i, vp, vp]
+        L.prl_hip_binarize_mokji_batch_device.argtypes = [i, i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_binarize_mokji_host.argtypes = [i, i, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_mokji_thresholds_batch_device.argtypes = [i, i, i, i, vp, sz, sz, i, i, vp, vp]
+        L.prl_hip_cooccurrence_batch_device.argtypes = [i, i, i, vp, sz, sz, vp, sz, sz, i, i, vp, vp]
+        L.prl_hip_mokji_threshold.argtypes = [vp, i, P(C.c_int)]
         _lib = L
     return _lib
 

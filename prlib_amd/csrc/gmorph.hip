@@ -555,6 +555,13 @@ int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& s
     return gm_run(plan, width, height, 1, false, src, dst, n_pages, tmp, nullptr, stream);
 }
 
+int gmorph_dilate_rect_run(int k, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
+                           hipStream_t stream)
+{
+    const GmPlan plan = gm_plan(PRL_MORPH_DILATE, PRL_SHAPE_RECT, k, k, false, false, false);
+    return gm_run(plan, width, height, 1, false, src, dst, n_pages, tmp, nullptr, stream);
+}
+
 }  // namespace prl_hip
 
 using namespace prl_hip;

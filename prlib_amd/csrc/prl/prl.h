@@ -19,6 +19,7 @@
 //   src/balance/balanceSimpleWhite.h:33                    prl::simpleWhiteBalance
 //   src/balance/balanceGrayWorldWhite.h:33                 prl::grayWorldWhiteBalance
 //   src/cleanBackgroundToWhite.h:40                        prl::cleanBackgroundToWhite
+//   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -129,6 +130,17 @@ CV_EXPORTS void gammaCorrection(const cv::Mat& inputImage, cv::Mat& outputImage,
 CV_EXPORTS void simpleWhiteBalance(const cv::Mat& inputImage, cv::Mat& outputImage, const double k);
 CV_EXPORTS void grayWorldWhiteBalance(const cv::Mat& inputImage, cv::Mat& outputImage, const double pNorm, const bool withMax);
 CV_EXPORTS void cleanBackgroundToWhite(const cv::Mat& inputImage, cv::Mat& outputImage);
+
+// src/binarizations/binarizeMokji.h:46 - one global threshold from the co-occurrence matrix of the page and its dilation
+// (binarizeMokji.cpp:35-94, mokji.hip; the arithmetic is stated in prl_hip.h): out = gray > t ? 255 : 0, 8UC1 at the input's size.
+// std::invalid_argument("mokjiThreshold: invalid maxEdgeWidth") for maxEdgeWidth < 1, then ("mokjiThreshold: invalid
+// minEdgeMagnitude") for minEdgeMagnitude < 1, both before the image is looked at.  cv::cvtColor(BGR2GRAY) runs unconditionally in
+// the reference: an empty or 1-channel Mat (and any count other than 3 and 4) is cv::Exception StsUnsupportedFormat, as is a depth
+// other than CV_8U.  Where the reference is undefined (no interior: cols <= 2 maxEdgeWidth or rows <= 2 maxEdgeWidth; no pair with
+// an edge of minEdgeMagnitude; minEdgeMagnitude >= 256) the page comes out all 255, which is what x86 gives.  Limit: maxEdgeWidth
+// above 127 on a page with an interior is StsBadArg.  On every error outputImage stays untouched.  The output is a new continuous
+// Mat; the input's pixels are never written (out may be in, or a view of it).
+CV_EXPORTS void binarizeMokji(const cv::Mat& inputImage, cv::Mat& outputImage, size_t maxEdgeWidth = 3, size_t minEdgeMagnitude = 20);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

@@ -274,6 +274,25 @@ void prl::cleanBackgroundToWhite(const cv::Mat& inputImage, cv::Mat& outputImage
     outputImage = result;
 }
 
+// binarizeMokji.cpp:35-94.  The reference's order: the two argument checks, then cv::cvtColor(BGR2GRAY) whatever the input is.
+// The C layer takes the gray page: with OpenCV present the conversion is the installed cv::cvtColor, as everywhere in this file.
+void prl::binarizeMokji(const cv::Mat& inputImage, cv::Mat& outputImage, size_t maxEdgeWidth, size_t minEdgeMagnitude)
+{
+    if (maxEdgeWidth < 1) throw std::invalid_argument("mokjiThreshold: invalid maxEdgeWidth");
+    if (minEdgeMagnitude < 1) throw std::invalid_argument("mokjiThreshold: invalid minEdgeMagnitude");
+    if (inputImage.empty() || (inputImage.channels() != 3 && inputImage.channels() != 4)) raise(PRL_ERR_BAD_CHANNELS);
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::binarizeMokji: 8-bit images only");
+    // into int without changing the result: 256 and above is "no pair"; 2^30 and above leaves no interior on any Mat
+    const int M = (int)(minEdgeMagnitude < 256 ? minEdgeMagnitude : 256);
+    const int E = (int)(maxEdgeWidth < ((size_t)1 << 30) ? maxEdgeWidth : ((size_t)1 << 30));
+    cv::Mat gray = inputImage;      // a header: the conversion gives it a buffer of its own, the input's pixels are only read
+    bgr2gray_inplace(gray);
+    cv::Mat result(gray.rows, gray.cols, CV_8UC1);
+    const int st = prl_hip_binarize_mokji_host(1, E, M, gray.data, gray.step, gray.cols, gray.rows, result.data, result.step);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
 namespace {
 
 constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255

@@ -407,6 +407,9 @@ int median_pass_pages(int width, int height, int channels, int ksize, const Page
 // batch, source and destination distinct; `tmp`: n_pages * width * height bytes; enqueues only (caller holds ctx->mu) ----------
 int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
                          hipStream_t stream);
+// DILATE with a k x k rectangle (k odd, 3..255), anchor at the centre: the same conditions and `tmp` (binarizeMokji, mokji.hip)
+int gmorph_dilate_rect_run(int k, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
+                           hipStream_t stream);
 
 // ---- morphology (morph.hip) ------------------------------------------------------------------
 int morph_run(int iterations, const PageSet& src, int n_pages, int width, int height,
