@@ -56,6 +56,8 @@ typedef enum prl_status {
     PRL_ERR_NO_DEVICE = 6,   /* no gfx950 device / HIP runtime unusable */
     PRL_ERR_HIP = 7,         /* a HIP call failed; see prl_hip_last_error_detail() */
     PRL_ERR_NOMEM = 8,       /* device or host allocation failed */
+    PRL_ERR_UNSUPPORTED = 10,/* a value the reference's interface accepts and this library does not provide (a border mode of
+                              * prl::warpCrop other than CONSTANT / REPLICATE) */
     PRL_ERR_LITERAL_BUDGET = 9 /* more pages of the call need the literal redo than prl_hip_set_literal_page_budget() allows:
                                   the masks of those pages are UNFINISHED (every other page is complete); see INTEGRATION.md §3 */
 } prl_status;
@@ -735,6 +737,91 @@ int prl_hip_rotate_host(int channels, double angle, const uint8_t* src, size_t s
                         size_t dst_step);
 int prl_hip_deskew_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step,
                         int* out_w, int* out_h, double* angle);
+
+/* ---- perspective crop (prl::warpCrop, src/warp.cpp:32-102, src/warp.h:49-73) -------------------------- */
+
+/*
+ * prl::warpCrop(in, out, x0, y0, ..., x3, y3, ratio, borderMode, borderValue) takes four corners (top left, top right, bottom
+ * right, bottom left) and returns the quadrilateral as a rectangle: a size rule, cv::getPerspectiveTransform and
+ * cv::warpPerspective(INTER_LINEAR).  The canonical arithmetic, float64 throughout with one rounding per written operation;
+ * [upstream] marks what is OpenCV's (3.4.4+ / 4.x: imgwarp.cpp, matrix_operations.cpp, the hal LU), as restated in
+ * tests/warp_ref.py.  Parity with an installed OpenCV is not pinned.
+ *
+ * Size (warp.cpp:42-53).  side1 = sqrt((x1-x0)^2 + (y1-y0)^2), side2 over corners 2, 3, side3 over 0, 3, side4 over 1, 2: the
+ * argument is the reference's `int` expression (it wraps like 32-bit two's complement; a negative one gives a NaN) converted to
+ * double.  W = cvRound(max(side1, side2)), H = cvRound(max(side3, side4)); if ratio > 0, W = cvRound(H / ratio).  max(a, b) is
+ * a < b ? b : a; cvRound rounds half to even, and a NaN or a value outside the int range gives INT_MIN [upstream, x86].
+ *
+ * Matrix [upstream]: cv::getPerspectiveTransform(src, dst) with dst = (0,0), (W,0), (W,H), (0,H).  The corners go through float
+ * (the reference's srcBuff / dstBuff), then to double.  For i = 0..3, with (sx, sy) -> (dx, dy):
+ *     a[i]   = {sx, sy, 1, 0, 0, 0, -sx*dx, -sy*dx}     b[i]   = dx
+ *     a[i+4] = {0, 0, 0, sx, sy, 1, -sx*dy, -sy*dy}     b[i+4] = dy
+ * solved by LU with partial pivoting: in column i the FIRST row of largest |a[j][i]| (strict >) is the pivot, the system is
+ * singular if that pivot is < 100 * DBL_EPSILON; d = -1 / a[i][i]; for the rows j below, alpha = a[j][i] * d,
+ * a[j][k] += alpha * a[i][k] (k > i), b[j] += alpha * b[i]; back substitution s = b[i], s -= a[i][k] * x[k] (k > i ascending),
+ * x[i] = s / a[i][i].  M = {x0 .. x7, 1}.  (OpenCV before 3.4.4 solved the system by SVD: not this.)
+ *
+ * Inversion [upstream]: cv::warpPerspective without WARP_INVERSE_MAP inverts M by cv::invert's closed form for 3 x 3:
+ *     det = m00*(m11*m22 - m12*m21) - m01*(m10*m22 - m12*m20) + m02*(m10*m21 - m11*m20),   d = 1 / det,
+ *     t = {(m11*m22 - m12*m21)*d, (m02*m21 - m01*m22)*d, (m01*m12 - m02*m11)*d,
+ *          (m12*m20 - m10*m22)*d, (m00*m22 - m02*m20)*d, (m02*m10 - m00*m12)*d,
+ *          (m10*m21 - m11*m20)*d, (m01*m20 - m00*m21)*d, (m00*m11 - m01*m10)*d}.
+ *
+ * Per pixel (x, y) of the ow x oh result [upstream], M now the inverted matrix.  OpenCV walks the result in blocks and the
+ * block width enters the arithmetic: bh = min(16, oh), bw = min(1024 / bh, ow) (integer division), xb = (x / bw) * bw,
+ * x1 = x - xb.  Per row of a block, each sum left to right:
+ *     X0 = M[0]*xb + M[1]*y + M[2]      Y0 = M[3]*xb + M[4]*y + M[5]      W0 = M[6]*xb + M[7]*y + M[8]
+ * and per pixel
+ *     W = W0 + M[6]*x1;  W = W ? 32.0 / W : 0
+ *     fX = max(-2^31, min(2^31 - 1, (X0 + M[0]*x1) * W))      fY likewise      (min(a, b) is b < a ? b : a: a NaN gives 2^31 - 1)
+ *     X = fX rounded half to even, Y likewise;  sx = clamp(X >> 5, -32768, 32767), sy likewise;  fx = X & 31, fy = Y & 31
+ * then the four taps (sx, sy), (sx+1, sy), (sx, sy+1), (sx+1, sy+1) with the weights 32(32-fx)(32-fy), 32 fx (32-fy),
+ * 32(32-fx) fy, 32 fx fy and out = (sum v*w + 2^14) >> 15 per channel.  A tap is inside iff 0 <= its x < width and
+ * 0 <= its y < height, tested per tap.  PRL_BORDER_CONSTANT: an outside tap takes saturate_cast<uchar>(border_value[c]) =
+ * clamp(cvRound(border_value[c]), 0, 255); PRL_BORDER_REPLICATE: the tap's coordinates are clamped to the page.  Any other border
+ * mode is PRL_ERR_UNSUPPORTED.
+ *
+ * Limits, all PRL_ERR_BAD_ARG (the reference has none of them): page or result sides above 32767; W <= 0 or H <= 0 after the
+ * rounding; a singular 8 x 8 system or det == 0; an entry of the given or of the inverted matrix that is not finite or exceeds
+ * 2^500 in magnitude (no intermediate value can then become a NaN).
+ */
+#define PRL_BORDER_CONSTANT 0    /* cv::BORDER_CONSTANT */
+#define PRL_BORDER_REPLICATE 1   /* cv::BORDER_REPLICATE */
+
+/* The size rule alone: what a caller sizes its destination with.  Host code, no device needed.  PRL_ERR_BAD_ARG for a null
+ * pointer and for a size outside 1..32767 (nothing is written then). */
+int prl_hip_warp_crop_size(const int32_t quad[8], double ratio, int* out_w, int* out_h);
+
+/* cv::getPerspectiveTransform as stated above: four (x, y) pairs each way, M = 9 doubles in row order.  Host code, no device
+ * needed.  PRL_ERR_BAD_ARG for a null pointer or a singular system (M is not written then). */
+int prl_hip_perspective_transform(const double src_xy[8], const double dst_xy[8], double M[9]);
+
+/*
+ * cv::warpPerspective(src, dst, M_i, Size(out_wh[2i], out_wh[2i+1]), INTER_LINEAR [| WARP_INVERSE_MAP], border_mode,
+ * border_value) per page: `matrices` is a host array of 9 * n_pages doubles, inverse_map != 0 says they already map result ->
+ * source, out_wh a host array (INPUT) of 2 * n_pages sizes.  1..4 channels.  d_dst pages need room for the largest result, rows of
+ * dst_step bytes; bytes of a destination page outside its ow x oh are not written.  border_value: 4 doubles or NULL (zeros).
+ * In place is not allowed.  Enqueues on `stream` and returns: nothing is waited for but the previous call's record copy.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_CHANNELS;
+ * PRL_ERR_UNSUPPORTED (border mode); PRL_ERR_BAD_ARG (null pointer, negative n_pages, d_src == d_dst, step < row bytes, then
+ * the limits above per page).
+ */
+int prl_hip_warp_perspective_batch_device(int n_pages, int channels, const double* matrices, int inverse_map, const uint8_t* d_src,
+                                          size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                          size_t dst_page_stride, size_t dst_step, const int32_t* out_wh, int border_mode,
+                                          const double* border_value, void* stream);
+
+/* prl::warpCrop per page: `quads` is a host array of 8 * n_pages ints (x0, y0, ..., x3, y3), one `ratio` for the call; sizes and
+ * matrices as stated above; out_wh (host, OUTPUT, written on success) receives every page's W x H.  A caller sizes the destination
+ * beforehand with prl_hip_warp_crop_size.  Otherwise as prl_hip_warp_perspective_batch_device. */
+int prl_hip_warp_crop_batch_device(int n_pages, int channels, const int32_t* quads, double ratio, const uint8_t* d_src,
+                                   size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                   size_t dst_page_stride, size_t dst_step, int32_t* out_wh, int border_mode,
+                                   const double* border_value, void* stream);
+
+/* One host image (what the cv::Mat wrapper calls); dst holds the size prl_hip_warp_crop_size reports.  Synchronises. */
+int prl_hip_warp_crop_host(int channels, const int32_t quad[8], double ratio, const uint8_t* src, size_t src_step, int width,
+                           int height, uint8_t* dst, size_t dst_step, int border_mode, const double* border_value);
 
 #ifdef __cplusplus
 }

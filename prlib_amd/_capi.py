@@ -33,6 +33,7 @@ PRL_ERR_NO_DEVICE = 6
 PRL_ERR_HIP = 7
 PRL_ERR_NOMEM = 8
 PRL_ERR_LITERAL_BUDGET = 9
+PRL_ERR_UNSUPPORTED = 10
 
 SAUVOLA, NIBLACK, WOLFJOLION, NICK, FENG = range(5)
 MODE_AUTO, MODE_LITERAL = 0, 1
@@ -65,6 +66,8 @@ EXPORTED_SYMBOLS = [
     "prl_hip_gamma_lut", "prl_hip_clean_background_lut", "prl_hip_simple_white_balance_luts", "prl_hip_gray_world_luts",
     "prl_hip_binarize_mokji_batch_device", "prl_hip_binarize_mokji_host", "prl_hip_mokji_thresholds_batch_device",
     "prl_hip_cooccurrence_batch_device", "prl_hip_mokji_threshold",
+    "prl_hip_warp_crop_size", "prl_hip_perspective_transform", "prl_hip_warp_perspective_batch_device",
+    "prl_hip_warp_crop_batch_device", "prl_hip_warp_crop_host",
 ]
 
 
@@ -225,6 +228,11 @@ def lib() -> C.CDLL:
         L.prl_hip_mokji_thresholds_batch_device.argtypes = [i, i, i, i, vp, sz, sz, i, i, vp, vp]
         L.prl_hip_cooccurrence_batch_device.argtypes = [i, i, i, vp, sz, sz, vp, sz, sz, i, i, vp, vp]
         L.prl_hip_mokji_threshold.argtypes = [vp, i, P(C.c_int)]
+        L.prl_hip_warp_crop_size.argtypes = [vp, d, P(C.c_int), P(C.c_int)]
+        L.prl_hip_perspective_transform.argtypes = [vp, vp, vp]
+        L.prl_hip_warp_perspective_batch_device.argtypes = [i, i, vp, i, vp, sz, sz, i, i, vp, sz, sz, vp, i, vp, vp]
+        L.prl_hip_warp_crop_batch_device.argtypes = [i, i, vp, d, vp, sz, sz, i, i, vp, sz, sz, vp, i, vp, vp]
+        L.prl_hip_warp_crop_host.argtypes = [i, vp, d, vp, sz, i, i, vp, sz, i, vp]
         _lib = L
     return _lib
 

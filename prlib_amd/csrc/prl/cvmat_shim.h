@@ -17,6 +17,7 @@
 #include <memory>
 #include <exception>
 #include <string>
+#include <vector>
 
 #define CV_8U 0
 #define CV_CN_SHIFT 3
@@ -46,6 +47,35 @@ enum Code {   // opencv2/core/base.hpp
     GpuApiCallError = -217,
 };
 }  // namespace Error
+
+// opencv2/core/base.hpp
+enum BorderTypes {
+    BORDER_CONSTANT = 0,
+    BORDER_REPLICATE = 1,
+    BORDER_REFLECT = 2,
+    BORDER_WRAP = 3,
+    BORDER_REFLECT_101 = 4,
+    BORDER_TRANSPARENT = 5,
+};
+
+// opencv2/core/types.hpp: Point_<_Tp> with x, y and Scalar_<_Tp> with val[4] (prl::warpCrop's corner list and border value)
+template <typename _Tp> class Point_ {
+public:
+    Point_() : x(0), y(0) {}
+    Point_(_Tp _x, _Tp _y) : x(_x), y(_y) {}
+    _Tp x, y;
+};
+typedef Point_<int> Point2i;
+typedef Point2i Point;
+
+template <typename _Tp> class Scalar_ {
+public:
+    Scalar_() { val[0] = val[1] = val[2] = val[3] = 0; }
+    Scalar_(_Tp v0, _Tp v1, _Tp v2 = 0, _Tp v3 = 0) { val[0] = v0; val[1] = v1; val[2] = v2; val[3] = v3; }
+    Scalar_(_Tp v0) { val[0] = v0; val[1] = val[2] = val[3] = 0; }
+    _Tp val[4];
+};
+typedef Scalar_<double> Scalar;
 
 struct Size {
     int width = 0, height = 0;

@@ -20,6 +20,7 @@
 //   src/balance/balanceGrayWorldWhite.h:33                 prl::grayWorldWhiteBalance
 //   src/cleanBackgroundToWhite.h:40                        prl::cleanBackgroundToWhite
 //   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
+//   src/warp.h:49-73                                       prl::warpCrop
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -28,6 +29,8 @@
 // include/prl/ holds one forwarding header per reference header (binarizeSauvola.h, ..., denoiseNLM.h), so a caller keeps
 // its #include lines and only changes the include path.
 #pragma once
+
+#include <vector>
 
 #if defined(__has_include)
 #if __has_include(<opencv2/core/core.hpp>)
@@ -170,6 +173,22 @@ CV_EXPORTS double findAngle(const cv::Mat& inputImage);
 // src/deskew/deskew.h:52 - 0.0 (see prl_host.cpp: a no-op for the page prl::deskew hands it, deskew.cpp:70-84, :238).
 CV_EXPORTS double findOrientation(const cv::Mat& inputImage);
 CV_EXPORTS void rotate(const cv::Mat& inputImage, cv::Mat& outputImage, double angle);
+
+// src/warp.h:49-73 - the quadrilateral (x0, y0) top left, (x1, y1) top right, (x2, y2) bottom right, (x3, y3) bottom left as a
+// rectangle (warp.cpp:32-102, warp.hip; the arithmetic is stated in prl_hip.h): W = cvRound(max of the top and bottom sides),
+// H = cvRound(max of the left and right sides), W = cvRound(H / ratio) for ratio > 0, cv::getPerspectiveTransform,
+// cv::warpPerspective(INTER_LINEAR, borderMode, borderValue).  The defaults are the reference's: -1.0, cv::BORDER_CONSTANT
+// (written 0 here) and cv::Scalar().  The vector overload throws std::invalid_argument("Image for warping is empty") and
+// ("Size of array of base points for warping isn't equal 4") as warp.cpp:82-90 does; the coordinate overload has no check of its
+// own, so an empty input is cv::warpPerspective's cv::Exception StsAssert [upstream].  cv::Exception StsUnsupportedFormat for a
+// depth other than CV_8U or more than 4 channels; StsNotImplemented for a border mode other than cv::BORDER_CONSTANT and
+// cv::BORDER_REPLICATE; StsBadArg for the limits (sides above 32767, a result side <= 0, corners that give a singular system).
+// On every error outputImage stays untouched.  The output is a new continuous Mat; the input's pixels are never written.
+CV_EXPORTS void warpCrop(const cv::Mat& inputImage, cv::Mat& outputImage, const int x0, const int y0, const int x1, const int y1,
+              const int x2, const int y2, const int x3, const int y3, double ratio = -1.0, const int borderMode = 0,
+              const cv::Scalar& borderValue = cv::Scalar());
+CV_EXPORTS void warpCrop(cv::Mat& inputImage, cv::Mat& outputImage, const std::vector<cv::Point>& points, double ratio = -1.0,
+              int borderMode = 0, const cv::Scalar& borderValue = cv::Scalar());
 
 // BASELINE config 1 (plumbing, host only): global Otsu, the one global threshold the reference uses
 // (cv::threshold(..., THRESH_BINARY | THRESH_OTSU), src/deskew/deskew.cpp:224).  Not a GPU path.

@@ -42,6 +42,7 @@ namespace {
     case PRL_ERR_NO_DEVICE:
     case PRL_ERR_HIP: code = cv::Error::GpuApiCallError; break;
     case PRL_ERR_NOMEM: code = cv::Error::StsNoMem; break;
+    case PRL_ERR_UNSUPPORTED: code = cv::Error::StsNotImplemented; break;
     default: break;
     }
     fail_cv(code, detail.empty() ? msg : msg + " [" + detail + "]", func, line);
@@ -468,6 +469,36 @@ void prl::rotate(const cv::Mat& inputImage, cv::Mat& outputImage, double angle)
                              result.data, result.step);
     if (st != PRL_OK) raise(st);
     outputImage = result;
+}
+
+void prl::warpCrop(const cv::Mat& inputImage, cv::Mat& outputImage, const int x0, const int y0, const int x1, const int y1, const int x2,
+                   const int y2, const int x3, const int y3, double ratio, const int borderMode, const cv::Scalar& borderValue)
+{
+    if (inputImage.empty()) PRL_FAIL_CV(cv::Error::StsAssert, "!_src.empty()");  // [upstream] cv::warpPerspective's own check
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::warpCrop: 8-bit images only");
+    if (inputImage.channels() > 4) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::warpCrop: at most 4 channels");
+    if (borderMode != PRL_BORDER_CONSTANT && borderMode != PRL_BORDER_REPLICATE)
+        PRL_FAIL_CV(cv::Error::StsNotImplemented, "prl::warpCrop: border modes other than BORDER_CONSTANT and BORDER_REPLICATE are not provided");
+    const int32_t quad[8] = {x0, y0, x1, y1, x2, y2, x3, y3};
+    int ow = 0, oh = 0;
+    int st = prl_hip_warp_crop_size(quad, ratio, &ow, &oh);
+    if (st != PRL_OK) raise(st);
+    cv::Mat result(oh, ow, inputImage.type());
+    const double value[4] = {borderValue.val[0], borderValue.val[1], borderValue.val[2], borderValue.val[3]};
+    st = prl_hip_warp_crop_host(inputImage.channels(), quad, ratio, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows,
+                                result.data, result.step, borderMode, value);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
+void prl::warpCrop(cv::Mat& inputImage, cv::Mat& outputImage, const std::vector<cv::Point>& points, double ratio, int borderMode,
+                   const cv::Scalar& borderValue)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Image for warping is empty");   // warp.cpp:82-85
+    if (points.size() != 4) throw std::invalid_argument("Size of array of base points for warping isn't equal 4");   // :87-90
+    // (cvRound of an int coordinate is the coordinate, :92-99)
+    warpCrop(inputImage, outputImage, points[0].x, points[0].y, points[1].x, points[1].y, points[2].x, points[2].y, points[3].x,
+             points[3].y, ratio, borderMode, borderValue);
 }
 
 bool prl::deskew(const cv::Mat& inputImage, cv::Mat& outputImage)

@@ -1058,6 +1058,7 @@ const char* prl_hip_strerror(int status)
     case PRL_ERR_HIP: return "HIP runtime error";
     case PRL_ERR_NOMEM: return "out of memory";
     case PRL_ERR_LITERAL_BUDGET: return "literal-page budget exceeded: the flagged pages are unfinished";
+    case PRL_ERR_UNSUPPORTED: return "not provided: an option of the reference's interface this library does not implement";
     default: return "unknown status";
     }
 }

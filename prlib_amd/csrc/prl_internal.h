@@ -62,6 +62,7 @@ struct DeviceCtx {
     bool prof_valid = false;
     hipEvent_t last_use = nullptr;  // last use of scratch / small / pinned: device_acquire waits on it, DeviceRelease records it
     hipEvent_t stage_use = nullptr; // same for the staging area (`stage`): recorded by its last user (guarded by stage_mu)
+    hipEvent_t pinned_use = nullptr; // the last asynchronous copy OUT of `pinned` (warp.hip's page records): the host waits for it before it overwrites the block (guarded by mu)
     // The angle search of prl::deskew has its own workspace, lock and stream: in the chain it runs for the next pass
     // while the other stages of the current one use `scratch` / `small` (glue.hip).
     std::mutex ppht_mu;
