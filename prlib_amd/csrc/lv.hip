@@ -15,8 +15,18 @@
 //                result1 & result2 is false, which zeroes the pixel in pass 3); without filters the final mask
 //   k_lv_final   pass 3: cv::adaptiveThreshold(G, 127, MEAN_C, BINARY, 15, 0) through a 78 x 46 LDS tile (sliding box sums), then
 //                ((A - N) > minResultVariance)
-// Bound: vector issue and LDS in all three passes (profiles/r02/pmc_stages.txt), not HBM.  WithoutFilters is integer-exact against
-// the oracle; the filtered variant is compared under a tolerance (float32 log / exp / pow differ between libraries).
+// Bound: vector issue and LDS in all three passes (profiles/r02/pmc_stages.txt), not HBM.
+// What the tests hold (tests/test_lv_gpu.py, tests/lv_ref.py).  WithoutFilters equals the oracle on every byte.  The filtered variant
+// is cut at the two 8-bit maps pass 2 leaves in scratch, the only inexact quantities (prl_hip_internal_lv_maps of the test-hooks
+// build hands them out, with the per-page constants, after the product entry's own launch sequence):
+//   before them  variances, result1, result2 (N == 255) and the per-channel thresholds are float32 arithmetic with a fixed order on
+//                integer-valued sums: exact, bit for bit
+//   G and N      go through the device's logf / expf / powf, which differ from any other library's in the last bit: each byte is
+//                the nearest integer of its float64 value, |byte - value| <= 0.5 + 0.01 (logf within 2 ulp and two additions
+//                on |l| <= 29: 1e-5 on the log map; over a log-map range >= 15 and gamma <= 3 that is 3e-3 on G, 2e-3 on N)
+//   after them   k_lv_final is integer: exact on the device's own maps
+// Against the oracle's float32 libm path the whole mask still differs on a pixel now and then where G or N sits on a rounding
+// boundary, so that comparison keeps its stated allowance (<= 1e-3 of the pixels; measured ~1e-5).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -346,11 +356,12 @@ __global__ void __launch_bounds__(256) k_lv_final(LvParams p, const uint8_t* __r
 
 using namespace prl_hip;
 
-extern "C" {
-
-int prl_hip_binarize_lv_batch_device(int n_pages, int with_filters, double coeff, int min_result_variance, double gamma,
-                                     const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
-                                     uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
+// The launch sequence of the C entry and of the test-hooks entry below.  out_G / out_N / out_consts (device memory; all null from
+// the product entry, all set and n_pages <= 16384 from the hooks entry): after the last kernel, on the same stream and before
+// the workspace is released, the dense n x height x width planes of G and N and the eight floats per page of LvConsts.
+static int lv_run(int n_pages, int with_filters, double coeff, int min_result_variance, double gamma, const uint8_t* d_src,
+                  size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                  size_t dst_step, uint8_t* out_G, uint8_t* out_N, float* out_consts, void* stream)
 {
     if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;  // binarizeByLocalVariances.cpp:16-19, :151-154
     if (n_pages < 0 || !d_src || !d_dst || src_step < (size_t)width * 3 || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
@@ -391,8 +402,38 @@ int prl_hip_binarize_lv_batch_device(int n_pages, int with_filters, double coeff
         if (with_filters) hipLaunchKernelGGL(k_lv_final, grid, dim3(256), 0, hs, p, G, NR, plane, d);
         PRL_HIP_CHECK(hipGetLastError());
     }
+    if (out_G) {
+        const size_t dense = (size_t)width * height;
+        PRL_HIP_CHECK(hipMemcpy2DAsync(out_G, dense, G, plane, dense, (size_t)n_pages, hipMemcpyDeviceToDevice, hs));
+        PRL_HIP_CHECK(hipMemcpy2DAsync(out_N, dense, NR, plane, dense, (size_t)n_pages, hipMemcpyDeviceToDevice, hs));
+        PRL_HIP_CHECK(hipMemcpyAsync(out_consts, d_consts, (size_t)n_pages * sizeof(LvConsts), hipMemcpyDeviceToDevice, hs));
+    }
     return PRL_OK;
 }
+
+extern "C" {
+
+int prl_hip_binarize_lv_batch_device(int n_pages, int with_filters, double coeff, int min_result_variance, double gamma,
+                                     const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
+                                     uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
+{
+    return lv_run(n_pages, with_filters, coeff, min_result_variance, gamma, d_src, src_page_stride, src_step, width, height, d_dst,
+                  dst_page_stride, dst_step, nullptr, nullptr, nullptr, stream);
+}
+
+#ifdef PRL_TEST_HOOKS
+// libprlib_hip_testhooks.so only: the filtered variant through the product entry's own launch sequence, and what pass 2 left in
+// scratch.  d_G, d_N: n_pages x height x width bytes; d_consts: n_pages x 8 floats (thr[3], ga, gb, lmean, two of padding); all
+// three in device memory.  At most 16384 pages (one chunk: the scratch of a later chunk overwrites the one before it).
+int prl_hip_internal_lv_maps(int n_pages, double coeff, int min_result_variance, double gamma, const uint8_t* d_src,
+                             size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                             size_t dst_step, uint8_t* d_G, uint8_t* d_N, float* d_consts, void* stream)
+{
+    if (n_pages > 16384 || !d_G || !d_N || !d_consts) return PRL_ERR_BAD_ARG;
+    return lv_run(n_pages, 1, coeff, min_result_variance, gamma, d_src, src_page_stride, src_step, width, height, d_dst,
+                  dst_page_stride, dst_step, d_G, d_N, d_consts, stream);
+}
+#endif
 
 int prl_hip_binarize_lv_host(int with_filters, double coeff, int min_result_variance, double gamma, const uint8_t* src,
                              size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
