@@ -237,6 +237,16 @@ def lib() -> C.CDLL:
     return _lib
 
 
+def stream_on(where) -> int:
+    """Makes the device of a tensor (or a torch.device) the library's current one and returns the handle of torch's current
+    stream on it: what every *_device entry is given."""
+    import torch
+
+    device = where.device if isinstance(where, torch.Tensor) else where
+    check(lib().prl_hip_set_device(device.index or 0))
+    return torch.cuda.current_stream(device).cuda_stream
+
+
 def check(status: int) -> None:
     if status != PRL_OK:
         L = lib()

@@ -16,7 +16,7 @@ import math
 
 import numpy as np
 
-from . import _capi
+from . import _capi, _pages
 
 ADAPTIVE_THRESH_MEAN_C, ADAPTIVE_THRESH_GAUSSIAN_C = 0, 1
 THRESH_BINARY, THRESH_BINARY_INV = 0, 1
@@ -33,43 +33,10 @@ def _run(image, p, out, gray_only=False):
     import ctypes as C
 
     L = _capi.lib()
-    if isinstance(image, np.ndarray):
-        if image.dtype != np.uint8 or image.ndim not in ((2,) if gray_only else (2, 3)):
-            raise TypeError("expected an H x W%s uint8 array" % ("" if gray_only else " [x C]"))
-        img = image if image.ndim == 3 else image[:, :, None]
-        if img.strides[2] != 1 or img.strides[1] != img.shape[2] or img.strides[0] < 0:
-            img = np.ascontiguousarray(img)
-        h, w, c = img.shape
-        res = np.empty((h, w), np.uint8) if out is None else out
-        if not isinstance(res, np.ndarray) or res.shape != (h, w) or res.dtype != np.uint8 or not res.flags.c_contiguous:
-            raise TypeError("out must be a C-contiguous H x W uint8 array")
-        _capi.check(L.prl_hip_binarize_adaptive_host(C.byref(p), c, img.ctypes.data, img.strides[0], w, h, res.ctypes.data, max(w, 1)))
-        return res
-    import torch
-
-    t = image
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in ((2, 3) if gray_only else (2, 3, 4)):
-        raise TypeError("expected a uint8 CUDA tensor [N,] H x W%s or a numpy uint8 array" % ("" if gray_only else " [x C]"))
-    if t.dim() == 2:
-        t4, batched = t[None, :, :, None], False
-    elif t.dim() == 3:
-        single = not gray_only and t.shape[-1] <= 4
-        t4, batched = (t[None], False) if single else (t[:, :, :, None], True)
-    else:
-        t4, batched = t, True
-    n, h, w, c = t4.shape
-    if (t4.stride(3) != 1 and c > 1) or t4.stride(2) != c:
-        t4 = t4.contiguous()
-    shape = (n, h, w) if batched else (h, w)
-    res = torch.empty(shape, dtype=torch.uint8, device=t.device) if out is None else out
-    if tuple(res.shape) != shape or res.dtype != torch.uint8 or res.device != t.device or (w > 1 and res.stride(-1) != 1):
-        raise TypeError("out must be a uint8 tensor [N,] H x W on the input's device, pixels dense")
-    r3 = res if batched else res[None]
-    _capi.check(L.prl_hip_set_device(t.device.index or 0))
-    stream = torch.cuda.current_stream(t.device).cuda_stream
-    _capi.check(L.prl_hip_binarize_adaptive_batch_device(C.byref(p), n, c, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h,
-                                                         r3.data_ptr(), r3.stride(0), r3.stride(1), stream))
-    return res
+    return _pages.run(image, _pages.same,
+                      lambda *a: L.prl_hip_binarize_adaptive_host(C.byref(p), *a),
+                      lambda n, *a: L.prl_hip_binarize_adaptive_batch_device(C.byref(p), n, *a), out, gray_only=gray_only,
+                      drop_channel=True)
 
 
 def _channels(image):

@@ -40,8 +40,7 @@ def backgroundNormalization(inputImage, out=None):
     n, h, w, c = t4.shape
     och = 1 if c == 1 else 3
     res = torch.empty((n, h, w, och), dtype=torch.uint8, device=t.device) if out is None else out.view(n, h, w, och)
-    _capi.check(L.prl_hip_set_device(t.device.index or 0))
-    stream = torch.cuda.current_stream(t.device).cuda_stream
+    stream = _capi.stream_on(t)
     _capi.check(L.prl_hip_bgnorm_batch_device(n, c, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h, res.data_ptr(),
                                               res.stride(0), res.stride(1), stream))
     if t.dim() == 2:

@@ -141,9 +141,7 @@ def finish(device=None) -> None:
     import torch
 
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(dev.index or 0))
-    _capi.check(L.prl_hip_finish(torch.cuda.current_stream(dev).cuda_stream))
+    _capi.check(_capi.lib().prl_hip_finish(_capi.stream_on(dev)))
 
 
 def set_literal_page_budget(max_pages: int) -> None:
@@ -214,8 +212,7 @@ def _binarize_torch(pages, params: BinarizeParams, out=None):
     if out.dim() != 3 or out.shape[0] != n or out.shape[1] != g.out_h or out.shape[2] < g.out_w or out.stride(2) != 1:
         raise ValueError("output buffer has the wrong shape")
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(pages.device.index or 0))
-    stream = torch.cuda.current_stream(pages.device).cuda_stream
+    stream = _capi.stream_on(pages)
     st = L.prl_hip_binarize_batch_device(
         C.byref(params), n, pages.data_ptr(), pages.stride(0), pages.stride(1), w, h,
         out.data_ptr(), out.stride(0), out.stride(1), stream)
@@ -262,8 +259,6 @@ def binarizeFeng(inputImage, windowSize: int = 21, thresholdCoefficient_alpha1: 
 
 def morph(mask, iterations: int, out=None):
     """The dilate/erode pair of binarizeSauvola.cpp:125-134 on a CUDA uint8 mask ([N,] H x W)."""
-    import torch
-
     squeeze = mask.dim() == 2
     if squeeze:
         mask = mask.unsqueeze(0)
@@ -271,8 +266,7 @@ def morph(mask, iterations: int, out=None):
     if out is None:
         out, _ = alloc_output(n, w, h, mask.device)
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(mask.device.index or 0))
-    stream = torch.cuda.current_stream(mask.device).cuda_stream
+    stream = _capi.stream_on(mask)
     _capi.check(L.prl_hip_morph_batch_device(int(iterations), n, mask.data_ptr(), mask.stride(0), mask.stride(1),
                                              w, h, out.data_ptr(), out.stride(0), out.stride(1), stream))
     res = out[:, :, :w]
@@ -302,8 +296,7 @@ def _lv(inputImage, with_filters, coeff, min_result_variance, gamma, out=None):
         raise TypeError("expected a uint8 CUDA tensor [N,] H x W x 3")
     n, h, w = t.shape[:3]
     o = torch.empty((n, h, w), dtype=torch.uint8, device=t.device) if out is None else (out.unsqueeze(0) if out.dim() == 2 else out)
-    _capi.check(L.prl_hip_set_device(t.device.index or 0))
-    stream = torch.cuda.current_stream(t.device).cuda_stream
+    stream = _capi.stream_on(t)
     _capi.check(L.prl_hip_binarize_lv_batch_device(n, with_filters, coeff, min_result_variance, gamma, t.data_ptr(), t.stride(0),
                                                    t.stride(1), w, h, o.data_ptr(), o.stride(0), o.stride(1), stream))
     return o[0] if squeeze else o

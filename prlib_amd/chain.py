@@ -37,13 +37,6 @@ def _pages(t, channels_last: bool):
     return t, squeeze
 
 
-def _stream(t):
-    import torch
-
-    _capi.check(_capi.lib().prl_hip_set_device(t.device.index or 0))
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
 def cvtColorBGR2GRAY(image, out=None):
     """[N,] H x W x 3|4 (BGR / BGRA) -> [N,] H x W."""
     import torch
@@ -54,7 +47,7 @@ def cvtColorBGR2GRAY(image, out=None):
         raise ValueError("expected 3 or 4 channels")
     o = torch.empty((n, h, w), dtype=torch.uint8, device=t.device) if out is None else (out.unsqueeze(0) if out.dim() == 2 else out)
     _capi.check(_capi.lib().prl_hip_bgr2gray_batch_device(n, c, t.data_ptr(), t.stride(0), t.stride(1), w, h,
-                                                         o.data_ptr(), o.stride(0), o.stride(1), _stream(t)))
+                                                         o.data_ptr(), o.stride(0), o.stride(1), _capi.stream_on(t)))
     return o[0] if squeeze else o
 
 
@@ -68,7 +61,7 @@ def cvtColorGRAY2BGR(image, channels: int = 3, out=None):
         raise ValueError("expected 3 or 4 channels")
     o = torch.empty((n, h, w, channels), dtype=torch.uint8, device=t.device) if out is None else (out.unsqueeze(0) if out.dim() == 3 else out)
     _capi.check(_capi.lib().prl_hip_gray2bgr_batch_device(n, channels, t.data_ptr(), t.stride(0), t.stride(1), w, h,
-                                                         o.data_ptr(), o.stride(0), o.stride(1), _stream(t)))
+                                                         o.data_ptr(), o.stride(0), o.stride(1), _capi.stream_on(t)))
     return o[0] if squeeze else o
 
 
@@ -80,7 +73,7 @@ def bitwise_not(image, out=None):
     n, h, w = t.shape
     o = torch.empty_like(t) if out is None else (out.unsqueeze(0) if out.dim() == 2 else out)
     _capi.check(_capi.lib().prl_hip_invert_batch_device(n, t.data_ptr(), t.stride(0), t.stride(1), w, h,
-                                                       o.data_ptr(), o.stride(0), o.stride(1), _stream(t)))
+                                                       o.data_ptr(), o.stride(0), o.stride(1), _capi.stream_on(t)))
     return o[0] if squeeze else o
 
 
@@ -122,7 +115,7 @@ def process_pages(pages, channels: int, method: int = 0, windowSize: int = 101, 
         wh = np.zeros((n, 2), dtype=np.int32)
         ang = np.zeros(n, dtype=np.float64)
         _capi.check(L.prl_hip_chain_pages_device(C.byref(cp), n, channels, t.data_ptr(), t.stride(0), t.stride(1), w, h,
-                                                o.data_ptr(), o.stride(0), o.stride(1), wh.ctypes.data, ang.ctypes.data, _stream(t)))
+                                                o.data_ptr(), o.stride(0), o.stride(1), wh.ctypes.data, ang.ctypes.data, _capi.stream_on(t)))
         res = [o[i, : wh[i, 1], : wh[i, 0]] for i in range(n)]
         return (res[0], ang[0]) if squeeze else (res, ang)
 
@@ -147,7 +140,7 @@ def process_pages(pages, channels: int, method: int = 0, windowSize: int = 101, 
     if tuple(o.shape) != (n, g.out_h, g.out_w) or o.stride(2) != 1:
         raise ValueError("output tensor has the wrong shape")
     _capi.check(L.prl_hip_chain_batch_device(C.byref(cp), n, channels, t.data_ptr(), t.stride(0), t.stride(1), w, h,
-                                            o.data_ptr(), o.stride(0), o.stride(1), _stream(t)))
+                                            o.data_ptr(), o.stride(0), o.stride(1), _capi.stream_on(t)))
     return o[0] if squeeze else o
 
 

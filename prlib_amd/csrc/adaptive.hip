@@ -33,7 +33,6 @@ namespace prl_hip {
 namespace {
 
 constexpr int kAdMaxBlock = 255;   // the weights travel as kernel arguments: (bs + 1) / 2 floats
-constexpr int kAdMaxSide = 32768;
 constexpr size_t kAdChunkBytes = (size_t)4 << 30;   // scratch per group of launches at most (one page at least)
 
 struct AdCfg {
@@ -264,29 +263,82 @@ int adaptive_run(const AdSpec& sp, int W, int H, const PageSet& s, const PageSet
     return PRL_OK;
 }
 
-bool ranges_overlap(const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b_bytes)
-{
-    return a < b + b_bytes && b < a + a_bytes;
-}
-
 AdSpec spec_of(const prl_adaptive_params* p)
 {
     return AdSpec{p->method, p->type, p->block_size, p->auto_invert, p->max_value, p->delta};
 }
 
-// statuses of the composed entry, before any device is touched
-int binarize_check(const prl_adaptive_params* p, int n_pages, int channels, const uint8_t* src, size_t src_step, int width, int height,
-                   const uint8_t* dst, size_t dst_step)
+// statuses of the composed entry, before any device is touched; batch: the *_batch_device entry
+int binarize_check(const prl_adaptive_params* p, const PageArgs& a, int channels, bool batch)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (!p) return PRL_ERR_BAD_ARG;
-    const int st = spec_window(spec_of(p));
+    st = spec_window(spec_of(p));
     if (st != PRL_OK) return st;
     if (p->median_ksize < 0 || (p->median_ksize != 0 && (p->median_ksize & 1) == 0)) return PRL_ERR_BAD_WINDOW;
     if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
-    if (n_pages < 0 || !src || !dst || src_step < (size_t)width * channels || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    if (width > kAdMaxSide || height > kAdMaxSide || p->median_ksize > 65535) return PRL_ERR_BAD_ARG;
+    if ((st = pages_rows_ok(a, channels, 1, batch)) != PRL_OK) return st;
+    if (pages_sides_ok(a) != PRL_OK || p->median_ksize > 65535) return PRL_ERR_BAD_ARG;
+    // never in place: every output reads its neighbours' inputs
+    if (batch && (st = pages_overlap_ok(a, channels, 1, false)) != PRL_OK) return st;
     return spec_args(spec_of(p));
+}
+
+int binarize_batch_device(const prl_adaptive_params* p, int channels, const PageArgs& a, void* stream)
+{
+    int st = binarize_check(p, a, channels, true);
+    if (st != PRL_OK) return st;
+    if (a.n_pages == 0) return PRL_OK;
+    const int width = a.width, height = a.height;
+    const size_t R = (size_t)width * channels;
+    const AdSpec sp = spec_of(p);
+    const bool med = p->median_ksize >= 3, color = channels > 1;
+    const bool med_color = med && color && p->median_on_color;
+    // planes per page in the scratch: A = the first stage's result when two stages precede the threshold, G = the gray page
+    // the threshold reads when any does
+    const size_t gray = r256((size_t)width * height);
+    const size_t a_bytes = (med && color) ? (med_color ? r256(R * (size_t)height) : gray) : 0;
+    const size_t g_bytes = (med || color) ? gray : 0;
+    const size_t per_page = a_bytes + g_bytes + ad_work_bytes(sp, width, height, 1) + 4;
+    const int chunk = stage_chunk(a.n_pages, per_page, kAdChunkBytes);
+    const size_t work_bytes = ad_work_bytes(sp, width, height, chunk);
+    WorkScope w;
+    st = w.open(stream, work_bytes + (a_bytes + g_bytes) * (size_t)chunk, 0, 0);
+    if (st != PRL_OK) return st;
+    const hipStream_t hs = w.stream;
+    uint8_t* work = w.scratch();
+    uint8_t* A = work + work_bytes;
+    uint8_t* G = A + a_bytes * (size_t)chunk;
+    for (int first = 0; first < a.n_pages; first += chunk) {
+        const int cnt = std::min(chunk, a.n_pages - first);
+        PageSet cur = src_pages(a, first);
+        const PageSetOut ga = page_set_out(G, gray, (size_t)width);
+        if (med_color) {   // binarizeAT.cpp / binarizeAGT.cpp: medianBlur on the colour page, then cvtColor
+            const PageSetOut pa = page_set_out(A, a_bytes, R);
+            st = median_pass_pages(width, height, channels, p->median_ksize, cur, pa, cnt, hs);
+            if (st != PRL_OK) return st;
+            st = prl_hip_bgr2gray_batch_device(cnt, channels, A, a_bytes, R, width, height, G, gray, (size_t)width, stream);
+            if (st != PRL_OK) return st;
+        } else if (color) {   // binarizeNativeAdaptive.cpp: cvtColor, then medianBlur
+            uint8_t* g1 = med ? A : G;
+            st = prl_hip_bgr2gray_batch_device(cnt, channels, cur.base, a.src_page_stride, a.src_step, width, height, g1, gray,
+                                               (size_t)width, stream);
+            if (st != PRL_OK) return st;
+            if (med) {
+                const PageSet pa = page_set(A, gray, (size_t)width);
+                st = median_pass_pages(width, height, 1, p->median_ksize, pa, ga, cnt, hs);
+                if (st != PRL_OK) return st;
+            }
+        } else if (med) {
+            st = median_pass_pages(width, height, 1, p->median_ksize, cur, ga, cnt, hs);
+            if (st != PRL_OK) return st;
+        }
+        if (med || color) cur = as_source(ga);
+        st = adaptive_run(sp, width, height, cur, dst_pages(a, first), cnt, work, hs);
+        if (st != PRL_OK) return st;
+    }
+    return PRL_OK;
 }
 
 }  // namespace
@@ -335,87 +387,18 @@ int prl_hip_binarize_adaptive_batch_device(const prl_adaptive_params* p, int n_p
                                            size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
                                            size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    int st = binarize_check(p, n_pages, channels, d_src, src_step, width, height, d_dst, dst_step);
-    if (st != PRL_OK) return st;
-    if (n_pages == 0) return PRL_OK;
-    const size_t R = (size_t)width * channels;
-    const size_t src_span = (size_t)(n_pages - 1) * src_page_stride + (size_t)(height - 1) * src_step + R;
-    const size_t dst_span = (size_t)(n_pages - 1) * dst_page_stride + (size_t)(height - 1) * dst_step + (size_t)width;
-    if (ranges_overlap(d_src, src_span, d_dst, dst_span)) return PRL_ERR_BAD_ARG;   // every output reads its neighbours' inputs
-    int dev;
-    st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const AdSpec sp = spec_of(p);
-    const bool med = p->median_ksize >= 3, color = channels > 1;
-    const bool med_color = med && color && p->median_on_color;
-    // planes per page in the scratch: A = the first stage's result when two stages precede the threshold, G = the gray page
-    // the threshold reads when any does
-    const size_t gray = r256((size_t)width * height);
-    const size_t a_bytes = (med && color) ? (med_color ? r256(R * (size_t)height) : gray) : 0;
-    const size_t g_bytes = (med || color) ? gray : 0;
-    const size_t per_page = a_bytes + g_bytes + ad_work_bytes(sp, width, height, 1) + 4;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(n_pages, 65535), kAdChunkBytes / per_page));
-    const size_t work_bytes = ad_work_bytes(sp, width, height, chunk);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const size_t need = work_bytes + (a_bytes + g_bytes) * (size_t)chunk;
-    if (need) {
-        st = ensure_scratch(ctx, need);
-        if (st != PRL_OK) return st;
-    }
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    uint8_t* work = static_cast<uint8_t*>(ctx->scratch);
-    uint8_t* A = work + work_bytes;
-    uint8_t* G = A + a_bytes * (size_t)chunk;
-    for (int first = 0; first < n_pages; first += chunk) {
-        const int cnt = std::min(chunk, n_pages - first);
-        const uint8_t* s0 = d_src + (size_t)first * src_page_stride;
-        PageSet cur = page_set(s0, src_page_stride, src_step);
-        const PageSetOut ga = page_set_out(G, gray, (size_t)width);
-        if (med_color) {   // binarizeAT.cpp / binarizeAGT.cpp: medianBlur on the colour page, then cvtColor
-            const PageSetOut a = page_set_out(A, a_bytes, R);
-            st = median_pass_pages(width, height, channels, p->median_ksize, cur, a, cnt, hs);
-            if (st != PRL_OK) return st;
-            st = prl_hip_bgr2gray_batch_device(cnt, channels, A, a_bytes, R, width, height, G, gray, (size_t)width, stream);
-            if (st != PRL_OK) return st;
-        } else if (color) {   // binarizeNativeAdaptive.cpp: cvtColor, then medianBlur
-            uint8_t* g1 = med ? A : G;
-            st = prl_hip_bgr2gray_batch_device(cnt, channels, s0, src_page_stride, src_step, width, height, g1, gray, (size_t)width,
-                                               stream);
-            if (st != PRL_OK) return st;
-            if (med) {
-                const PageSet a = page_set(A, gray, (size_t)width);
-                st = median_pass_pages(width, height, 1, p->median_ksize, a, ga, cnt, hs);
-                if (st != PRL_OK) return st;
-            }
-        } else if (med) {
-            st = median_pass_pages(width, height, 1, p->median_ksize, cur, ga, cnt, hs);
-            if (st != PRL_OK) return st;
-        }
-        if (med || color) {
-            cur.base = G; cur.page_stride = gray; cur.step = (size_t)width;
-        }
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
-        st = adaptive_run(sp, width, height, cur, d, cnt, work, hs);
-        if (st != PRL_OK) return st;
-    }
-    return PRL_OK;
+    return binarize_batch_device(p, channels, PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step},
+                                 stream);
 }
 
 int prl_hip_binarize_adaptive_host(const prl_adaptive_params* p, int channels, const uint8_t* src, size_t src_step, int width,
                                    int height, uint8_t* dst, size_t dst_step)
 {
-    const int st = binarize_check(p, 1, channels, src, src_step, width, height, dst, dst_step);
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const int st = binarize_check(p, a, channels, false);
     if (st != PRL_OK) return st;
-    const size_t in_row = (size_t)width * channels, out_row = (size_t)width;
-    return stage_host_page(src, src_step, in_row, height, dst, dst_step, out_row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return prl_hip_binarize_adaptive_batch_device(p, 1, channels, d_in, in_bytes, in_row, width, height,
-                                                                             d_out, out_bytes, out_row, s);
-                           });
+    return stage_host_pages(a, channels, 1, width, height,
+                            [&](const PageArgs& page, hipStream_t s) { return binarize_batch_device(p, channels, page, s); });
 }
 
 }  // extern "C"

@@ -344,29 +344,20 @@ int prl_hip_bgnorm_out_channels(int channels) { return channels == 1 ? 1 : 3; }
 int prl_hip_bgnorm_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
                                 int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;  // backgroundNormalization.cpp:40-43
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    int st = pages_nonempty(a);  // backgroundNormalization.cpp:40-43
+    if (st != PRL_OK) return st;
     if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;  // formatConvert.cpp:103-104
-    const int och = channels == 1 ? 1 : 3;
-    if (n_pages < 0 || !d_src || !d_dst || src_step < (size_t)width * channels || dst_step < (size_t)width * och)
-        return PRL_ERR_BAD_ARG;
+    if ((st = pages_rows_ok(a, channels, channels == 1 ? 1 : 3, true)) != PRL_OK) return st;
     if (height > 65535 || width > 40950) return PRL_ERR_BAD_ARG;  // grid.y; k_bg_maps' column flags
     if (n_pages == 0) return PRL_OK;
-    int dev;
-    int st = current_device(&dev);
+    const int chunk = stage_chunk(n_pages, 0, 0, 16384);
+    WorkScope w;
+    st = w.open(stream, bgnorm_work_bytes(chunk, channels, width, height), 0, 0);
     if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const int chunk = std::min(n_pages, 16384);
-    st = ensure_scratch(ctx, bgnorm_work_bytes(chunk, channels, width, height));
-    if (st != PRL_OK) return st;
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
     for (int first = 0; first < n_pages; first += chunk) {
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
-        st = bgnorm_run(std::min(chunk, n_pages - first), channels, s, width, height, d, ctx->scratch, hs);
+        st = bgnorm_run(std::min(chunk, n_pages - first), channels, src_pages(a, first), width, height, dst_pages(a, first), w.scratch(),
+                        w.stream);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;

@@ -36,7 +36,6 @@ namespace prl_hip {
 namespace {
 
 constexpr int kGmMaxK = 255;          // element sizes 1..255 (the spans travel as bytes in the kernel arguments)
-constexpr int kGmMaxSide = 32768;
 constexpr int kGmThreads = 256;
 constexpr int kGmItems = 4;           // output dwords per lane of k_gm_span
 constexpr int kGmLdsBytes = 64 * 1024;   // both level buffers of a workgroup: at least two workgroups per CU (160 KiB)
@@ -463,87 +462,57 @@ int gm_run(const GmPlan& plan, int W, int H, int C, bool literal, const PageSet&
     return PRL_OK;
 }
 
-bool gm_overlap(const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; }
-
 bool gm_known_op(int op)
 {
     return op == PRL_MORPH_ERODE || op == PRL_MORPH_DILATE || op == PRL_MORPH_OPEN || op == PRL_MORPH_CLOSE || op == PRL_MORPH_TOPHAT ||
            op == PRL_MORPH_BLACKHAT;
 }
 
-// the checks every entry makes, in the documented order (no device is touched)
-int gm_checks(int channels, int op, int shape, int kw, int kh, const uint8_t* src, size_t src_step, int width, int height,
-              const uint8_t* dst, size_t dst_step)
+struct GmOp { int op, shape, kw, kh; bool nuil; };
+
+// the checks every entry makes, in the documented order (no device is touched); batch: a *_batch_device entry
+int gm_checks(const PageArgs& a, int channels, const GmOp& o, bool batch)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (!gm_known_op(op) || shape < PRL_SHAPE_RECT || shape > PRL_SHAPE_ELLIPSE || kw < 1 || kh < 1 || kw > kGmMaxK || kh > kGmMaxK)
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
+    if (!gm_known_op(o.op) || o.shape < PRL_SHAPE_RECT || o.shape > PRL_SHAPE_ELLIPSE || o.kw < 1 || o.kh < 1 || o.kw > kGmMaxK ||
+        o.kh > kGmMaxK)
         return PRL_ERR_BAD_ARG;
     if (channels < 1 || channels > 4) return PRL_ERR_BAD_CHANNELS;
-    const size_t R = (size_t)width * channels;
-    if (!src || !dst || src_step < R || dst_step < R) return PRL_ERR_BAD_ARG;
-    if (width > kGmMaxSide || height > kGmMaxSide) return PRL_ERR_BAD_ARG;
-    return PRL_OK;
-}
-
-int gm_batch_device(int n_pages, int channels, int op, int shape, int kw, int kh, bool nuil, const uint8_t* d_src,
-                    size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
-                    size_t dst_step, void* stream)
-{
-    int st = gm_checks(channels, op, shape, kw, kh, d_src, src_step, width, height, d_dst, dst_step);
-    if (st != PRL_OK) return st;
-    if (n_pages < 0) return PRL_ERR_BAD_ARG;
-    if (n_pages == 0) return PRL_OK;
-    const size_t R = (size_t)width * channels;
-    const size_t src_span = (size_t)(n_pages - 1) * src_page_stride + (size_t)(height - 1) * src_step + R;
-    const size_t dst_span = (size_t)(n_pages - 1) * dst_page_stride + (size_t)(height - 1) * dst_step + R;
+    if ((st = pages_rows_ok(a, channels, channels, batch)) != PRL_OK) return st;
+    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
     // in place: the same pages at the same strides; any other overlap of source and destination is refused
-    const bool in_place = d_src == d_dst && src_page_stride == dst_page_stride && src_step == dst_step;
-    if (!in_place && gm_overlap(d_src, src_span, d_dst, dst_span)) return PRL_ERR_BAD_ARG;
-    int dev;
-    st = current_device(&dev);
+    return batch ? pages_overlap_ok(a, channels, channels, true) : PRL_OK;
+}
+
+int gm_batch_device(const PageArgs& a, int channels, const GmOp& o, void* stream)
+{
+    int st = gm_checks(a, channels, o, true);
     if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (a.n_pages == 0) return PRL_OK;
     const bool literal = env_knobs().gmorph_literal;
-    const GmPlan plan = gm_plan(op, shape, kw, kh, nuil, in_place, literal);
-    const size_t page_bytes = R * (size_t)height;
+    const GmPlan plan = gm_plan(o.op, o.shape, o.kw, o.kh, o.nuil, pages_in_place(a, channels, channels), literal);
+    const size_t page_bytes = (size_t)a.width * channels * (size_t)a.height;
     // pages per launch: grid.z, and at most 4 GiB of scratch (one page at least)
-    int chunk = std::min(n_pages, 65535);
-    if (plan.planes) chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, ((size_t)4 << 30) / (page_bytes * plan.planes)));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (plan.planes) {
-        st = ensure_scratch(ctx, page_bytes * (size_t)chunk * plan.planes);
-        if (st != PRL_OK) return st;
-    }
-    if (nuil) {
-        st = ensure_small(ctx, (size_t)chunk * 4 * sizeof(unsigned long long));
-        if (st != PRL_OK) return st;
-        ctx->lut_small[0] = ctx->lut_small[1] = nullptr;   // the block's head is overwritten
-    }
-    st = device_acquire(ctx, hs);
+    const int chunk = stage_chunk(a.n_pages, page_bytes * plan.planes);
+    WorkScope w;   // `scratch`: the plan's planes; `small`: correctNUIL's sums
+    st = w.open(stream, page_bytes * (size_t)chunk * plan.planes, o.nuil ? (size_t)chunk * 4 * sizeof(unsigned long long) : 0, 0);
     if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    for (int first = 0; first < n_pages; first += chunk) {
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
-        st = gm_run(plan, width, height, channels, literal, s, d, std::min(chunk, n_pages - first), static_cast<uint8_t*>(ctx->scratch),
-                    static_cast<unsigned long long*>(ctx->small), hs);
+    for (int first = 0; first < a.n_pages; first += chunk) {
+        st = gm_run(plan, a.width, a.height, channels, literal, src_pages(a, first), dst_pages(a, first), std::min(chunk, a.n_pages - first),
+                    w.scratch(), w.small<unsigned long long>(), w.stream);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
 }
 
-int gm_host(int channels, int op, int shape, int kw, int kh, bool nuil, const uint8_t* src, size_t src_step, int width, int height,
-            uint8_t* dst, size_t dst_step)
+int gm_host(int channels, const GmOp& o, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
 {
-    const int st = gm_checks(channels, op, shape, kw, kh, src, src_step, width, height, dst, dst_step);
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const int st = gm_checks(a, channels, o, false);
     if (st != PRL_OK) return st;
-    const size_t row = (size_t)width * channels;
-    return stage_host_page(src, src_step, row, height, dst, dst_step, row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return gm_batch_device(1, channels, op, shape, kw, kh, nuil, d_in, in_bytes, row, width, height, d_out,
-                                                      out_bytes, row, s);
-                           });
+    return stage_host_pages(a, channels, channels, width, height,
+                            [&](const PageArgs& page, hipStream_t s) { return gm_batch_device(page, channels, o, s); });
 }
 
 }  // namespace
@@ -572,28 +541,28 @@ int prl_hip_morphology_batch_device(int n_pages, int channels, int op, int shape
                                     size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
                                     size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    return gm_batch_device(n_pages, channels, op, shape, ksize_w, ksize_h, false, d_src, src_page_stride, src_step, width, height,
-                           d_dst, dst_page_stride, dst_step, stream);
+    return gm_batch_device(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
+                           GmOp{op, shape, ksize_w, ksize_h, false}, stream);
 }
 
 int prl_hip_morphology_host(int channels, int op, int shape, int ksize_w, int ksize_h, const uint8_t* src, size_t src_step, int width,
                             int height, uint8_t* dst, size_t dst_step)
 {
-    return gm_host(channels, op, shape, ksize_w, ksize_h, false, src, src_step, width, height, dst, dst_step);
+    return gm_host(channels, GmOp{op, shape, ksize_w, ksize_h, false}, src, src_step, width, height, dst, dst_step);
 }
 
 int prl_hip_correct_nuil_batch_device(int n_pages, int channels, int size, const uint8_t* d_src, size_t src_page_stride,
                                       size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
                                       void* stream)
 {
-    return gm_batch_device(n_pages, channels, PRL_MORPH_BLACKHAT, PRL_SHAPE_ELLIPSE, size, size, true, d_src, src_page_stride, src_step,
-                           width, height, d_dst, dst_page_stride, dst_step, stream);
+    return gm_batch_device(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
+                           GmOp{PRL_MORPH_BLACKHAT, PRL_SHAPE_ELLIPSE, size, size, true}, stream);
 }
 
 int prl_hip_correct_nuil_host(int channels, int size, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
                               size_t dst_step)
 {
-    return gm_host(channels, PRL_MORPH_BLACKHAT, PRL_SHAPE_ELLIPSE, size, size, true, src, src_step, width, height, dst, dst_step);
+    return gm_host(channels, GmOp{PRL_MORPH_BLACKHAT, PRL_SHAPE_ELLIPSE, size, size, true}, src, src_step, width, height, dst, dst_step);
 }
 
 }  // extern "C"

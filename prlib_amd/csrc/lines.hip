@@ -34,7 +34,6 @@ namespace {
 typedef unsigned long long u64;
 
 constexpr int kLnMinSide = 50;        // below it width / 50 == 0: cv::getStructuringElement asserts
-constexpr int kLnMaxSide = 32768;
 constexpr int kLnThreads = 256;
 constexpr int kLnLdsWords = 3840;     // words per level buffer; two buffers = 60 KiB: two workgroups per CU
 constexpr int kLnHWords = 2048;       // k_ln_hopen: words per level buffer aimed at (whole rows)
@@ -366,20 +365,20 @@ LnGeom ln_geom(int W, int H, int C)
     return g;
 }
 
-bool ln_overlap(const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; }
-
-// the checks every entry makes, in the documented order (no device is touched)
-int ln_checks(int channels, const uint8_t* src, size_t src_step, int width, int height, const uint8_t* dst, size_t dst_step)
+// the checks every entry makes, in the documented order (no device is touched); batch: the *_batch_device entry
+int ln_checks(const PageArgs& a, int channels, bool batch)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (channels != 1 && channels != 3) return PRL_ERR_BAD_CHANNELS;
-    if (width < kLnMinSide || height < kLnMinSide) {
+    if (a.width < kLnMinSide || a.height < kLnMinSide) {
         set_error_detail("removeLines: width / 50 or height / 50 is 0 (ksize.width > 0 && ksize.height > 0)");
         return PRL_ERR_BAD_ARG;
     }
-    if (!src || !dst || src_step < (size_t)width * channels || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    if (width > kLnMaxSide || height > kLnMaxSide) return PRL_ERR_BAD_ARG;
-    return PRL_OK;
+    if ((st = pages_rows_ok(a, channels, 1, batch)) != PRL_OK) return st;
+    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
+    // in place: 1-channel pages at the same strides (every source pixel is read before the first one is written)
+    return batch ? pages_overlap_ok(a, channels, 1, true) : PRL_OK;
 }
 
 size_t ln_scratch_per_page(const LnGeom& g, bool bytes)
@@ -444,46 +443,24 @@ int ln_run(const LnGeom& g, bool bytes, const PageSet& src, const PageSetOut& ds
     return PRL_OK;
 }
 
-int ln_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
-                    uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
+int ln_batch_device(const PageArgs& a, int channels, void* stream)
 {
-    int st = ln_checks(channels, d_src, src_step, width, height, d_dst, dst_step);
+    int st = ln_checks(a, channels, true);
     if (st != PRL_OK) return st;
-    if (n_pages < 0) return PRL_ERR_BAD_ARG;
-    const size_t R = (size_t)width * channels;
-    if (n_pages > 0) {
-        const size_t src_span = (size_t)(n_pages - 1) * src_page_stride + (size_t)(height - 1) * src_step + R;
-        const size_t dst_span = (size_t)(n_pages - 1) * dst_page_stride + (size_t)(height - 1) * dst_step + (size_t)width;
-        // in place: 1-channel pages at the same strides (every source pixel is read before the first one is written)
-        const bool in_place = channels == 1 && d_src == d_dst && src_page_stride == dst_page_stride && src_step == dst_step;
-        if (!in_place && ln_overlap(d_src, src_span, d_dst, dst_span)) return PRL_ERR_BAD_ARG;
-    }
-    if (n_pages == 0) return PRL_OK;
-    int dev;
-    st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const LnGeom g = ln_geom(width, height, channels);
+    if (a.n_pages == 0) return PRL_OK;
+    const LnGeom g = ln_geom(a.width, a.height, channels);
     const bool bytes = env_knobs().lines_bytes && g.L <= kLnBytesMaxK && g.Lv <= kLnBytesMaxK;
     const size_t per_page = ln_scratch_per_page(g, bytes);
     // pages per launch: grid.z, and at most 4 GiB of scratch (one page at least)
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(n_pages, 65535), ((size_t)4 << 30) / per_page));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    st = ensure_scratch(ctx, per_page * (size_t)chunk);
+    const int chunk = stage_chunk(a.n_pages, per_page);
+    WorkScope w;   // `small`: [bins of a chunk | Otsu thresholds of a chunk]
+    st = w.open(stream, per_page * (size_t)chunk, (size_t)chunk * (256 * sizeof(unsigned) + sizeof(int)), 0);
     if (st != PRL_OK) return st;
-    st = ensure_small(ctx, (size_t)chunk * (256 * sizeof(unsigned) + sizeof(int)));
-    if (st != PRL_OK) return st;
-    ctx->lut_small[0] = ctx->lut_small[1] = nullptr;   // the block's head is overwritten
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    unsigned* hist = static_cast<unsigned*>(ctx->small);
+    unsigned* hist = w.small<unsigned>();
     int* gthr = reinterpret_cast<int*>(hist + (size_t)chunk * 256);
-    for (int first = 0; first < n_pages; first += chunk) {
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
-        st = ln_run(g, bytes, s, d, std::min(chunk, n_pages - first), static_cast<uint8_t*>(ctx->scratch), hist, gthr, hs);
+    for (int first = 0; first < a.n_pages; first += chunk) {
+        st = ln_run(g, bytes, src_pages(a, first), dst_pages(a, first), std::min(chunk, a.n_pages - first), w.scratch(), hist, gthr,
+                    w.stream);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
@@ -500,19 +477,17 @@ extern "C" {
 int prl_hip_remove_lines_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
                                       int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    return ln_batch_device(n_pages, channels, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step,
+    return ln_batch_device(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
                            stream);
 }
 
 int prl_hip_remove_lines_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
 {
-    const int st = ln_checks(channels, src, src_step, width, height, dst, dst_step);
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const int st = ln_checks(a, channels, false);
     if (st != PRL_OK) return st;
-    return stage_host_page(src, src_step, (size_t)width * channels, height, dst, dst_step, (size_t)width, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return ln_batch_device(1, channels, d_in, in_bytes, (size_t)width * channels, width, height, d_out,
-                                                      out_bytes, (size_t)width, s);
-                           });
+    return stage_host_pages(a, channels, 1, width, height,
+                            [&](const PageArgs& page, hipStream_t s) { return ln_batch_device(page, channels, s); });
 }
 
 }  // extern "C"

@@ -32,7 +32,6 @@ namespace {
 constexpr int kMedWave = 64;
 constexpr int kMedRows = 30;    // output rows per lane of k_median_small (a multiple of 3 and 5: the ring's slots stay static)
 constexpr int kMedMaxK = 65535; // k^2 < 2^32
-constexpr int kMedMaxSide = 32768;
 
 __device__ __forceinline__ void ce(float& a, float& b)
 {
@@ -376,9 +375,40 @@ int median_run(const MedGeom& g, size_t times, const PageSet& src, const PageSet
     return PRL_OK;
 }
 
-bool ranges_overlap(const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b_bytes)
+// the checks of both entries, in the documented order (no device is touched); batch: the *_batch_device entry
+int median_checks(const PageArgs& a, int channels, int ksize, bool batch)
 {
-    return a < b + b_bytes && b < a + a_bytes;
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
+    if (ksize < 1 || (ksize & 1) == 0) return PRL_ERR_BAD_WINDOW;             // cv::medianBlur: ksize % 2 == 1
+    if (channels < 1 || channels > 4 || (channels == 2 && ksize >= 7)) return PRL_ERR_BAD_CHANNELS;   // k > 5: cn 1, 3, 4
+    if ((st = pages_rows_ok(a, channels, channels, batch)) != PRL_OK) return st;
+    if ((st = pages_sides_ok(a)) != PRL_OK || ksize > kMedMaxK) return PRL_ERR_BAD_ARG;
+    // in place: the same pages at the same strides; any other overlap of source and destination is refused
+    return batch ? pages_overlap_ok(a, channels, channels, true) : PRL_OK;
+}
+
+int median_batch_device(int channels, int ksize, size_t times, const PageArgs& a, void* stream)
+{
+    int st = median_checks(a, channels, ksize, true);
+    if (st != PRL_OK) return st;
+    if (a.n_pages == 0) return PRL_OK;
+    const bool work = ksize > 1 && times > 0;
+    const bool in_place = pages_in_place(a, channels, channels);
+    const bool need_tmp = work && (times >= 2 || in_place);
+    const MedGeom g = med_geom(a.width, a.height, channels, ksize);
+    const size_t page_bytes = (size_t)a.width * channels * (size_t)a.height;
+    // pages per launch: grid.z, and at most 4 GiB of scratch (one page at least)
+    const int chunk = stage_chunk(a.n_pages, need_tmp ? page_bytes : 0);
+    WorkScope w;
+    st = w.open(stream, need_tmp ? page_bytes * (size_t)chunk : 0, 0, 0);
+    if (st != PRL_OK) return st;
+    for (int first = 0; first < a.n_pages; first += chunk) {
+        st = median_run(g, work ? times : 0, src_pages(a, first), dst_pages(a, first), std::min(chunk, a.n_pages - first), in_place,
+                        need_tmp ? w.scratch() : nullptr, w.stream);
+        if (st != PRL_OK) return st;
+    }
+    return PRL_OK;
 }
 
 }  // namespace
@@ -400,62 +430,18 @@ int prl_hip_median_batch_device(int n_pages, int channels, int ksize, size_t tim
                                 size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
                                 void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (ksize < 1 || (ksize & 1) == 0) return PRL_ERR_BAD_WINDOW;             // cv::medianBlur: ksize % 2 == 1
-    if (channels < 1 || channels > 4 || (channels == 2 && ksize >= 7)) return PRL_ERR_BAD_CHANNELS;   // k > 5: cn 1, 3, 4
-    const size_t R = (size_t)width * channels;
-    if (n_pages < 0 || !d_src || !d_dst || src_step < R || dst_step < R) return PRL_ERR_BAD_ARG;
-    if (width > kMedMaxSide || height > kMedMaxSide || ksize > kMedMaxK) return PRL_ERR_BAD_ARG;
-    if (n_pages == 0) return PRL_OK;
-    const size_t src_span = (size_t)(n_pages - 1) * src_page_stride + (size_t)(height - 1) * src_step + R;
-    const size_t dst_span = (size_t)(n_pages - 1) * dst_page_stride + (size_t)(height - 1) * dst_step + R;
-    const bool work = ksize > 1 && times > 0;
-    // in place: the same pages at the same strides; any other overlap of source and destination is refused
-    const bool in_place = d_src == d_dst && src_page_stride == dst_page_stride && src_step == dst_step;
-    if (!in_place && ranges_overlap(d_src, src_span, d_dst, dst_span)) return PRL_ERR_BAD_ARG;
-    const bool need_tmp = work && (times >= 2 || in_place);
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const MedGeom g = med_geom(width, height, channels, ksize);
-    const size_t page_bytes = R * (size_t)height;
-    // pages per launch: grid.z, and at most 4 GiB of scratch (one page at least)
-    int chunk = std::min(n_pages, 65535);
-    if (need_tmp) chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, ((size_t)4 << 30) / page_bytes));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (need_tmp) {
-        st = ensure_scratch(ctx, page_bytes * (size_t)chunk);
-        if (st != PRL_OK) return st;
-    }
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    for (int first = 0; first < n_pages; first += chunk) {
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
-        st = median_run(g, work ? times : 0, s, d, std::min(chunk, n_pages - first), in_place,
-                        need_tmp ? static_cast<uint8_t*>(ctx->scratch) : nullptr, hs);
-        if (st != PRL_OK) return st;
-    }
-    return PRL_OK;
+    return median_batch_device(channels, ksize, times,
+                               PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, stream);
 }
 
 int prl_hip_median_host(int channels, int ksize, size_t times, const uint8_t* src, size_t src_step, int width, int height,
                         uint8_t* dst, size_t dst_step)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (ksize < 1 || (ksize & 1) == 0) return PRL_ERR_BAD_WINDOW;
-    if (channels < 1 || channels > 4 || (channels == 2 && ksize >= 7)) return PRL_ERR_BAD_CHANNELS;
-    const size_t row = (size_t)width * channels;
-    if (!src || !dst || src_step < row || dst_step < row) return PRL_ERR_BAD_ARG;
-    if (width > kMedMaxSide || height > kMedMaxSide || ksize > kMedMaxK) return PRL_ERR_BAD_ARG;
-    return stage_host_page(src, src_step, row, height, dst, dst_step, row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return prl_hip_median_batch_device(1, channels, ksize, times, d_in, in_bytes, row, width, height, d_out,
-                                                                  out_bytes, row, s);
-                           });
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const int st = median_checks(a, channels, ksize, false);
+    if (st != PRL_OK) return st;
+    return stage_host_pages(a, channels, channels, width, height,
+                            [&](const PageArgs& page, hipStream_t s) { return median_batch_device(channels, ksize, times, page, s); });
 }
 
 }  // extern "C"

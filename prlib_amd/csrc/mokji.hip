@@ -25,7 +25,6 @@ namespace prl_hip {
 
 namespace {
 
-constexpr int kMkMaxSide = 32768;
 constexpr int kMkMaxE = 127;                        // the dilation's element is 2E + 1 <= 255 wide (gmorph.hip)
 constexpr int kMkThreads = 256;
 constexpr int kMkCoocThreads = 1024;
@@ -217,25 +216,24 @@ __global__ __launch_bounds__(kMkThreads) void k_mokji_apply(PageSet gray, PageSe
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 
-bool mk_overlap(const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; }
-
 bool mk_interior_empty(int width, int height, long long border) { return width <= 2 * border || height <= 2 * border; }
 
-// the checks of the binarizer and of the thresholds entry, in the documented order (no device is touched); dst == nullptr and
-// dst_step == 0 with has_dst == false
-int mk_checks(int channels, int E, int M, const uint8_t* src, size_t src_step, int width, int height, bool has_dst, const uint8_t* dst,
-              size_t dst_step)
+// the checks of the binarizer and of the thresholds entry (which has no destination: with_mask == false), in the documented order
+// (no device is touched); batch: a *_batch_device entry
+int mk_checks(const PageArgs& a, int channels, int E, int M, bool with_mask, bool batch)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (E < 1 || M < 1) return PRL_ERR_BAD_ARG;
-    if (E > kMkMaxE && !mk_interior_empty(width, height, E)) {
+    if (E > kMkMaxE && !mk_interior_empty(a.width, a.height, E)) {
         set_error_detail("binarizeMokji: maxEdgeWidth above 127 (a dilation element above 255) on a page with an interior");
         return PRL_ERR_BAD_ARG;
     }
     if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
-    if (!src || (has_dst && !dst) || src_step < (size_t)width * channels || (has_dst && dst_step < (size_t)width)) return PRL_ERR_BAD_ARG;
-    if (width > kMkMaxSide || height > kMkMaxSide) return PRL_ERR_BAD_ARG;
-    return PRL_OK;
+    if ((st = pages_rows_ok(a, channels, with_mask ? 1 : 0, batch)) != PRL_OK) return st;
+    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
+    // in place: 1-channel pages at the same strides (every statistic is taken before the first pixel is written)
+    return batch ? pages_overlap_ok(a, channels, with_mask ? 1 : 0, true) : PRL_OK;
 }
 
 // workgroups per page of k_mokji_cooc: about two per CU over the call, at least 8 interior rows each, at most 64
@@ -329,50 +327,24 @@ int mk_run(const MkGeom& g, const PageSet& src, const PageSetOut* dst, int n, ui
     return PRL_OK;
 }
 
-// d_dst != nullptr: the binarizer (thresholds in the device's small block); else d_thr receives the thresholds
-int mk_batch_device(int n_pages, int channels, int E, int M, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
-                    int height, bool with_mask, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, int32_t* d_thr, void* stream)
+// with_mask: the binarizer (thresholds in the device's small block); else d_thr receives the thresholds
+int mk_batch_device(const PageArgs& a, int channels, int E, int M, bool with_mask, int32_t* d_thr, void* stream)
 {
-    int st = mk_checks(channels, E, M, d_src, src_step, width, height, with_mask, d_dst, dst_step);
+    int st = mk_checks(a, channels, E, M, with_mask, true);
     if (st != PRL_OK) return st;
-    if (n_pages < 0 || (!with_mask && !d_thr)) return PRL_ERR_BAD_ARG;
-    if (with_mask && n_pages > 0) {
-        const size_t src_span = (size_t)(n_pages - 1) * src_page_stride + (size_t)(height - 1) * src_step + (size_t)width * channels;
-        const size_t dst_span = (size_t)(n_pages - 1) * dst_page_stride + (size_t)(height - 1) * dst_step + (size_t)width;
-        // in place: 1-channel pages at the same strides (every statistic is taken before the first pixel is written)
-        const bool in_place = channels == 1 && d_src == d_dst && src_page_stride == dst_page_stride && src_step == dst_step;
-        if (!in_place && mk_overlap(d_src, src_span, d_dst, dst_span)) return PRL_ERR_BAD_ARG;
-    }
-    if (n_pages == 0) return PRL_OK;
-    int dev;
-    st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const MkGeom g = mk_geom(width, height, channels, E, M);
+    if (!with_mask && !d_thr) return PRL_ERR_BAD_ARG;
+    if (a.n_pages == 0) return PRL_OK;
+    const MkGeom g = mk_geom(a.width, a.height, channels, E, M);
     const size_t per_page = mk_scratch_per_page(g, with_mask);
     // pages per launch: grid.y, and at most 4 GiB of scratch (one page at least)
-    int chunk = std::min(n_pages, 65535);
-    if (per_page) chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)chunk, ((size_t)4 << 30) / per_page));
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (per_page) {
-        st = ensure_scratch(ctx, per_page * (size_t)chunk);
-        if (st != PRL_OK) return st;
-    }
-    if (with_mask) {
-        st = ensure_small(ctx, (size_t)chunk * sizeof(int));
-        if (st != PRL_OK) return st;
-        ctx->lut_small[0] = ctx->lut_small[1] = nullptr;   // the block's head is overwritten
-    }
-    st = device_acquire(ctx, hs);
+    const int chunk = stage_chunk(a.n_pages, per_page);
+    WorkScope w;
+    st = w.open(stream, per_page * (size_t)chunk, with_mask ? (size_t)chunk * sizeof(int) : 0, 0);
     if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    for (int first = 0; first < n_pages; first += chunk) {
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
-        int* thr = with_mask ? static_cast<int*>(ctx->small) : d_thr + first;
-        st = mk_run(g, s, with_mask ? &d : nullptr, std::min(chunk, n_pages - first), static_cast<uint8_t*>(ctx->scratch), thr,
-                    ctx->cu_count, hs);
+    for (int first = 0; first < a.n_pages; first += chunk) {
+        const PageSetOut d = dst_pages(a, first);
+        st = mk_run(g, src_pages(a, first), with_mask ? &d : nullptr, std::min(chunk, a.n_pages - first), w.scratch(),
+                    with_mask ? w.small<int>() : d_thr + first, w.ctx->cu_count, w.stream);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
@@ -390,50 +362,49 @@ int prl_hip_binarize_mokji_batch_device(int n_pages, int channels, int max_edge_
                                         size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
                                         size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    return mk_batch_device(n_pages, channels, max_edge_width, min_edge_magnitude, d_src, src_page_stride, src_step, width, height, true,
-                           d_dst, dst_page_stride, dst_step, nullptr, stream);
+    return mk_batch_device(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
+                           max_edge_width, min_edge_magnitude, true, nullptr, stream);
 }
 
 int prl_hip_binarize_mokji_host(int channels, int max_edge_width, int min_edge_magnitude, const uint8_t* src, size_t src_step, int width,
                                 int height, uint8_t* dst, size_t dst_step)
 {
-    const int st = mk_checks(channels, max_edge_width, min_edge_magnitude, src, src_step, width, height, true, dst, dst_step);
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const int st = mk_checks(a, channels, max_edge_width, min_edge_magnitude, true, false);
     if (st != PRL_OK) return st;
-    const size_t in_row = (size_t)width * channels;
-    return stage_host_page(src, src_step, in_row, height, dst, dst_step, (size_t)width, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return mk_batch_device(1, channels, max_edge_width, min_edge_magnitude, d_in, in_bytes, in_row, width,
-                                                      height, true, d_out, out_bytes, (size_t)width, nullptr, s);
-                           });
+    return stage_host_pages(a, channels, 1, width, height, [&](const PageArgs& page, hipStream_t s) {
+        return mk_batch_device(page, channels, max_edge_width, min_edge_magnitude, true, nullptr, s);
+    });
 }
 
 int prl_hip_mokji_thresholds_batch_device(int n_pages, int channels, int max_edge_width, int min_edge_magnitude, const uint8_t* d_src,
                                           size_t src_page_stride, size_t src_step, int width, int height, int32_t* d_thresholds,
                                           void* stream)
 {
-    return mk_batch_device(n_pages, channels, max_edge_width, min_edge_magnitude, d_src, src_page_stride, src_step, width, height, false,
-                           nullptr, 0, 0, d_thresholds, stream);
+    return mk_batch_device(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, nullptr, 0, 0}, channels, max_edge_width,
+                           min_edge_magnitude, false, d_thresholds, stream);
 }
 
 int prl_hip_cooccurrence_batch_device(int n_pages, int border, int min_diff, const uint8_t* d_a, size_t a_page_stride, size_t a_step,
                                       const uint8_t* d_b, size_t b_page_stride, size_t b_step, int width, int height, uint32_t* d_cooc,
                                       void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    const PageArgs a{n_pages, d_a, a_page_stride, a_step, width, height, nullptr, 0, 0};
+    const PageArgs b{n_pages, d_b, b_page_stride, b_step, width, height, nullptr, 0, 0};
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (border < 0 || min_diff < 0 || min_diff > 256) return PRL_ERR_BAD_ARG;
-    if (!d_a || !d_b || !d_cooc || n_pages < 0 || a_step < (size_t)width || b_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    if (width > kMkMaxSide || height > kMkMaxSide) return PRL_ERR_BAD_ARG;
+    if (pages_rows_ok(a, 1, 0, true) != PRL_OK || pages_rows_ok(b, 1, 0, true) != PRL_OK || !d_cooc) return PRL_ERR_BAD_ARG;
+    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
     if (n_pages == 0) return PRL_OK;
-    int dev;
-    const int st0 = current_device(&dev);
-    if (st0 != PRL_OK) return st0;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    for (int first = 0; first < n_pages; first += 65535) {
-        const int n = std::min(65535, n_pages - first);
-        const int st = mk_cooc_launch(pages_from(page_set(d_a, a_page_stride, a_step), first),
-                                      pages_from(page_set(d_b, b_page_stride, b_step), first), n, width, height, border, min_diff,
-                                      d_cooc + (size_t)first * 256 * 256, ctx->cu_count, hs);
+    int dev;   // no workspace and no lock: the device check alone
+    st = current_device(&dev);
+    if (st != PRL_OK) return st;
+    const int cu_count = device_ctx(dev)->cu_count;
+    const int chunk = stage_chunk(n_pages, 0);
+    for (int first = 0; first < n_pages; first += chunk) {
+        st = mk_cooc_launch(src_pages(a, first), src_pages(b, first), std::min(chunk, n_pages - first), width, height, border, min_diff,
+                            d_cooc + (size_t)first * 256 * 256, cu_count, static_cast<hipStream_t>(stream));
         if (st != PRL_OK) return st;
     }
     return PRL_OK;

@@ -111,6 +111,7 @@ const EnvKnobs& env_knobs()
         k.median_generic = geti("PRL_HIP_MEDIAN_GENERIC", 0) != 0;
         k.gmorph_literal = geti("PRL_HIP_GMORPH_LITERAL", 0) != 0;
         k.lines_bytes = geti("PRL_HIP_LINES_BYTES", 0) != 0;
+        k.stage_chunk_pages = (int)std::max(0ll, std::min(65535ll, geti("PRL_HIP_STAGE_CHUNK", 0)));
         k.segmax_cap = (unsigned)std::max(64ll, std::min(1ll << 20, geti("PRL_HIP_SEGMAX_CAP", 1 << 20)));
         k.force_exact = geti("PRL_HIP_FORCE_EXACT", 0) != 0;
 #endif

@@ -14,6 +14,7 @@
 #include <string>
 
 #include "../../include/prl_hip.h"
+#include "page_args.h"
 
 namespace prl_hip {
 
@@ -132,6 +133,7 @@ struct EnvKnobs {
     bool median_generic = false;  // PRL_HIP_MEDIAN_GENERIC=1  the histogram kernel for every window (median.hip), k = 3 and 5 included
     bool gmorph_literal = false;  // PRL_HIP_GMORPH_LITERAL=1  the by-the-definition kernel for every element (gmorph.hip)
     bool lines_bytes = false;     // PRL_HIP_LINES_BYTES=1     removeLines' openings on byte masks through k_gm_span (lines.hip)
+    int stage_chunk_pages = 0;    // PRL_HIP_STAGE_CHUNK=n     (tests) the stage entries take at most n pages per chunk (stage_chunk below; 0: off)
 };
 const EnvKnobs& env_knobs();
 
@@ -164,6 +166,45 @@ struct DeviceRelease {
     DeviceCtx* c; hipStream_t s;
     ~DeviceRelease() { (void)hipEventRecord(c->last_use, s); }
 };
+// One call on the shared workspace, from the checks' end to the return: open() takes the current device, its context and `mu`,
+// grows the blocks the call asks for (0 bytes: not needed), drops NL-means' cached tables whenever `small` is asked for (its
+// head is about to be overwritten) and makes the stream wait for the previous user.  On every exit after a successful open()
+// the call's work is recorded as the new last use before `mu` is released, as DeviceRelease does.
+class WorkScope {
+public:
+    DeviceCtx* ctx = nullptr;
+    hipStream_t stream = nullptr;
+    int open(void* stream_arg, size_t scratch_bytes, size_t small_bytes, size_t pinned_bytes)
+    {
+        int dev;
+        int st = current_device(&dev);
+        if (st != PRL_OK) return st;
+        ctx = device_ctx(dev);
+        stream = static_cast<hipStream_t>(stream_arg);
+        lk_ = std::unique_lock<std::mutex>(ctx->mu);
+        if (scratch_bytes && (st = ensure_scratch(ctx, scratch_bytes)) != PRL_OK) return st;
+        if (small_bytes && (st = ensure_small(ctx, small_bytes)) != PRL_OK) return st;
+        if (pinned_bytes && (st = ensure_pinned(ctx, pinned_bytes)) != PRL_OK) return st;
+        if (small_bytes) ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
+        st = device_acquire(ctx, stream);
+        acquired_ = st == PRL_OK;
+        return st;
+    }
+    ~WorkScope() { if (acquired_) (void)hipEventRecord(ctx->last_use, stream); }   // (lk_ is released after this body)
+    template <typename T = uint8_t> T* scratch() const { return static_cast<T*>(ctx->scratch); }
+    template <typename T = uint8_t> T* small() const { return static_cast<T*>(ctx->small); }
+    template <typename T = uint8_t> T* pinned() const { return static_cast<T*>(ctx->pinned); }
+private:
+    std::unique_lock<std::mutex> lk_;
+    bool acquired_ = false;
+};
+// Pages per chunk of a stage entry: pages_per_chunk (page_args.h), capped by the test hook PRL_HIP_STAGE_CHUNK - the one place
+// that reads it - so that a handful of small pages runs the second chunk's offsets of every entry.
+inline int stage_chunk(int n_pages, size_t per_page_bytes, size_t budget_bytes = (size_t)4 << 30, int grid_limit = 65535)
+{
+    const int chunk = pages_per_chunk(n_pages, per_page_bytes, budget_bytes, grid_limit), cap = env_knobs().stage_chunk_pages;
+    return cap > 0 ? std::min(chunk, cap) : chunk;
+}
 int ensure_stage(DeviceCtx* ctx, size_t bytes);  // caller holds stage_mu
 // The staging area is shared by every stream of the device: a user makes its stream wait for the previous user's work
 // (stage_acquire) before the first write and records its own work at the end (stage_release).  Caller holds stage_mu.
@@ -251,6 +292,23 @@ inline Set pages_from(Set s, int first)
     if (s.table) s.table += first;
     else if (s.base) s.base += (size_t)first * s.page_stride;
     return s;
+}
+// the pages of a stage entry's arguments from page `first` on
+inline PageSet src_pages(const PageArgs& a, int first) { return pages_from(page_set(a.src, a.src_page_stride, a.src_step), first); }
+inline PageSetOut dst_pages(const PageArgs& a, int first) { return pages_from(page_set_out(a.dst, a.dst_page_stride, a.dst_step), first); }
+
+// A *_host stage entry after its checks: the page `h` describes (host pointers; in_channels / out_channels bytes per pixel, the
+// result out_width x out_height) goes through stage_host_page, and
+//     int run(const PageArgs& page, hipStream_t stream)
+// gets the staging area as a one-page batch of the same width and height.
+template <typename Run>
+int stage_host_pages(const PageArgs& h, int in_channels, int out_channels, int out_width, int out_height, Run&& run)
+{
+    const size_t in_row = (size_t)h.width * in_channels, out_row = (size_t)out_width * out_channels;
+    return stage_host_page(h.src, h.src_step, in_row, h.height, h.dst, h.dst_step, out_row, out_height,
+                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
+                               return run(PageArgs{1, d_in, in_bytes, in_row, h.width, h.height, d_out, out_bytes, out_row}, s);
+                           });
 }
 
 // Threshold constants shared by the literal and fused kernels (host-prepared, passed by value).

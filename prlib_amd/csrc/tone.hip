@@ -31,7 +31,6 @@ size_t bgnorm_work_bytes(int n_pages, int channels, int width, int height);
 
 namespace {
 
-constexpr int kToneMaxSide = 32768;
 constexpr int kToneThreads = 256;
 constexpr int kTonePx = 8;            // pixels per thread of k_tone_lut
 constexpr int kToneChunk = 16384;     // pages per launch (grid.y / grid.z; 3840 bytes of tables and bins per page)
@@ -313,33 +312,18 @@ __global__ __launch_bounds__(kToneThreads) void k_tone_put(ToneTab tab, uint8_t*
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 
-struct ToneImg {   // the page arguments every entry shares
-    int n_pages;
-    const uint8_t* src; size_t src_page_stride, src_step;
-    int width, height;
-    uint8_t* dst; size_t dst_page_stride, dst_step;
-};
-
-bool tone_overlap(const uint8_t* a, size_t a_bytes, const uint8_t* b, size_t b_bytes) { return a < b + b_bytes && b < a + a_bytes; }
-
 // the checks every entry makes, in the documented order (no device is touched).  channels_ok: the entry's own rule; oc: channels
-// of the result (0: the entry has no destination).
-int tone_checks(const ToneImg& a, bool channels_ok, int channels, int oc, bool device)
+// of the result (0: the entry has no destination); batch: a *_batch_device entry (a page count, and source and destination may
+// meet)
+int tone_checks(const PageArgs& a, bool channels_ok, int channels, int oc, bool batch)
 {
-    if (a.width <= 0 || a.height <= 0) return PRL_ERR_EMPTY;
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (!channels_ok) return PRL_ERR_BAD_CHANNELS;
-    if (!a.src || (oc && !a.dst) || (device && a.n_pages < 0)) return PRL_ERR_BAD_ARG;
-    const size_t in_row = (size_t)a.width * channels, out_row = (size_t)a.width * oc;
-    if (a.src_step < in_row || (oc && a.dst_step < out_row)) return PRL_ERR_BAD_ARG;
-    if (a.width > kToneMaxSide || a.height > kToneMaxSide) return PRL_ERR_BAD_ARG;
-    if (device && oc && a.n_pages > 0) {
-        const size_t src_span = (size_t)(a.n_pages - 1) * a.src_page_stride + (size_t)(a.height - 1) * a.src_step + in_row;
-        const size_t dst_span = (size_t)(a.n_pages - 1) * a.dst_page_stride + (size_t)(a.height - 1) * a.dst_step + out_row;
-        // in place: as many channels out as in, at the same strides (a thread reads its pixels before it writes them)
-        const bool in_place = oc == channels && a.src == a.dst && a.src_page_stride == a.dst_page_stride && a.src_step == a.dst_step;
-        if (!in_place && tone_overlap(a.src, src_span, a.dst, dst_span)) return PRL_ERR_BAD_ARG;
-    }
-    return PRL_OK;
+    if ((st = pages_rows_ok(a, channels, oc, batch)) != PRL_OK) return st;
+    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
+    // in place: as many channels out as in, at the same strides (a thread reads its pixels before it writes them)
+    return batch ? pages_overlap_ok(a, channels, oc, true) : PRL_OK;
 }
 
 int hist_launch(int channels, const PageSet& src, int n, int W, int H, unsigned* hist, hipStream_t stream)
@@ -371,56 +355,27 @@ int lut_launch(int channels, int oc, const PageSet& src, const PageSetOut& dst, 
     return PRL_OK;
 }
 
-PageSet src_pages(const ToneImg& a, int first) { return pages_from(page_set(a.src, a.src_page_stride, a.src_step), first); }
-PageSetOut dst_pages(const ToneImg& a, int first) { return pages_from(page_set_out(a.dst, a.dst_page_stride, a.dst_step), first); }
-
-// The workspace of a call that needs one: `small` holds [bins of a chunk | tables of a chunk], `scratch` what bgnorm asks for.
-struct ToneWork {
-    DeviceCtx* ctx = nullptr;
-    hipStream_t hs = nullptr;
-};
-int tone_device(ToneWork* w, void* stream)
-{
-    int dev;
-    const int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    w->ctx = device_ctx(dev);
-    w->hs = static_cast<hipStream_t>(stream);
-    return PRL_OK;
-}
-
 // one table for every page and channel: gamma, the clean-background curve
-int shared_table_run(const ToneImg& a, int channels, int oc, const ToneTab& tab, bool bgnorm_first, void* stream)
+int shared_table_run(const PageArgs& a, int channels, int oc, const ToneTab& tab, bool bgnorm_first, void* stream)
 {
     if (a.n_pages == 0) return PRL_OK;
-    ToneWork w;
-    int st = tone_device(&w, stream);
+    const int chunk = stage_chunk(a.n_pages, 0, 0, kToneChunk);
+    WorkScope w;   // `small`: the table; `scratch`: what bgnorm asks for
+    int st = w.open(stream, bgnorm_first ? bgnorm_work_bytes(chunk, channels, a.width, a.height) : 0, 4 * 256, 0);
     if (st != PRL_OK) return st;
-    DeviceCtx* ctx = w.ctx;
-    const int chunk = std::min(a.n_pages, kToneChunk);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    if (bgnorm_first) {
-        st = ensure_scratch(ctx, bgnorm_work_bytes(chunk, channels, a.width, a.height));
-        if (st != PRL_OK) return st;
-    }
-    st = ensure_small(ctx, 4 * 256);
-    if (st != PRL_OK) return st;
-    ctx->lut_small[0] = ctx->lut_small[1] = nullptr;   // the block's head is overwritten
-    st = device_acquire(ctx, w.hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, w.hs};
-    uint8_t* lut = static_cast<uint8_t*>(ctx->small);
-    hipLaunchKernelGGL(k_tone_put, dim3((unsigned)oc), dim3(kToneThreads), 0, w.hs, tab, lut);
+    const hipStream_t hs = w.stream;
+    uint8_t* lut = w.small();
+    hipLaunchKernelGGL(k_tone_put, dim3((unsigned)oc), dim3(kToneThreads), 0, hs, tab, lut);
     PRL_HIP_CHECK(hipGetLastError());
     for (int first = 0; first < a.n_pages; first += chunk) {
         const int n = std::min(chunk, a.n_pages - first);
         const PageSetOut d = dst_pages(a, first);
         if (bgnorm_first) {
-            st = bgnorm_run(n, channels, src_pages(a, first), a.width, a.height, d, ctx->scratch, w.hs);
+            st = bgnorm_run(n, channels, src_pages(a, first), a.width, a.height, d, w.scratch(), hs);
             if (st != PRL_OK) return st;
-            st = lut_launch(oc, oc, as_source(d), d, n, a.width, a.height, lut, 0, w.hs);
+            st = lut_launch(oc, oc, as_source(d), d, n, a.width, a.height, lut, 0, hs);
         } else {
-            st = lut_launch(channels, oc, src_pages(a, first), d, n, a.width, a.height, lut, 0, w.hs);
+            st = lut_launch(channels, oc, src_pages(a, first), d, n, a.width, a.height, lut, 0, hs);
         }
         if (st != PRL_OK) return st;
     }
@@ -428,50 +383,39 @@ int shared_table_run(const ToneImg& a, int channels, int oc, const ToneTab& tab,
 }
 
 // simpleWhiteBalance (mode 0) and grayWorld (mode 1): 3 channels, a table set per page from the page's histograms
-int derived_table_run(const ToneImg& a, int mode, double param, int with_max, void* stream)
+int derived_table_run(const PageArgs& a, int mode, double param, int with_max, void* stream)
 {
     if (a.n_pages == 0) return PRL_OK;
-    ToneWork w;
-    int st = tone_device(&w, stream);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = w.ctx;
     const bool on_host = mode == kDeriveGrayWorld1 && !(param == 1.0);
-    const int chunk = std::min(a.n_pages, kToneChunk);
+    const int chunk = stage_chunk(a.n_pages, 0, 0, kToneChunk);
     const size_t hist_bytes = (size_t)chunk * 3 * 256 * sizeof(unsigned), lut_bytes = (size_t)chunk * 3 * 256;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    st = ensure_small(ctx, hist_bytes + lut_bytes);
+    WorkScope w;   // `small` (and `pinned` for tables built on the host): [bins of a chunk | tables of a chunk]
+    int st = w.open(stream, 0, hist_bytes + lut_bytes, on_host ? hist_bytes + lut_bytes : 0);
     if (st != PRL_OK) return st;
-    if (on_host) {
-        st = ensure_pinned(ctx, hist_bytes + lut_bytes);
-        if (st != PRL_OK) return st;
-    }
-    ctx->lut_small[0] = ctx->lut_small[1] = nullptr;   // the block's head is overwritten
-    st = device_acquire(ctx, w.hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, w.hs};
-    unsigned* hist = static_cast<unsigned*>(ctx->small);
-    uint8_t* lut = static_cast<uint8_t*>(ctx->small) + hist_bytes;
+    const hipStream_t hs = w.stream;
+    unsigned* hist = w.small<unsigned>();
+    uint8_t* lut = w.small() + hist_bytes;
     for (int first = 0; first < a.n_pages; first += chunk) {
         const int n = std::min(chunk, a.n_pages - first);
         const PageSet s = src_pages(a, first);
-        st = hist_launch(3, s, n, a.width, a.height, hist, w.hs);
+        st = hist_launch(3, s, n, a.width, a.height, hist, hs);
         if (st != PRL_OK) return st;
         if (!on_host) {
-            hipLaunchKernelGGL(k_tone_derive, dim3((unsigned)n), dim3(kToneThreads), 0, w.hs, mode, param, with_max, a.width, a.height, hist,
+            hipLaunchKernelGGL(k_tone_derive, dim3((unsigned)n), dim3(kToneThreads), 0, hs, mode, param, with_max, a.width, a.height, hist,
                                lut);
             PRL_HIP_CHECK(hipGetLastError());
         } else {
             // pow with a general exponent is the host libm's: the bins come down, the tables go up, the stream is drained twice
-            unsigned* h_hist = static_cast<unsigned*>(ctx->pinned);
-            uint8_t* h_lut = static_cast<uint8_t*>(ctx->pinned) + hist_bytes;
-            PRL_HIP_CHECK(hipMemcpyAsync(h_hist, hist, (size_t)n * 3 * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, w.hs));
-            PRL_HIP_CHECK(hipStreamSynchronize(w.hs));
+            unsigned* h_hist = w.pinned<unsigned>();
+            uint8_t* h_lut = w.pinned() + hist_bytes;
+            PRL_HIP_CHECK(hipMemcpyAsync(h_hist, hist, (size_t)n * 3 * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, hs));
+            PRL_HIP_CHECK(hipStreamSynchronize(hs));
             for (int i = 0; i < n; ++i)
                 gw_tables(param, with_max, h_hist + (size_t)i * 3 * 256, a.width * a.height, h_lut + (size_t)i * 3 * 256);
-            PRL_HIP_CHECK(hipMemcpyAsync(lut, h_lut, (size_t)n * 3 * 256, hipMemcpyHostToDevice, w.hs));
-            PRL_HIP_CHECK(hipStreamSynchronize(w.hs));   // the pinned block is the next call's too
+            PRL_HIP_CHECK(hipMemcpyAsync(lut, h_lut, (size_t)n * 3 * 256, hipMemcpyHostToDevice, hs));
+            PRL_HIP_CHECK(hipStreamSynchronize(hs));   // the pinned block is the next call's too
         }
-        st = lut_launch(3, 3, s, dst_pages(a, first), n, a.width, a.height, lut, (size_t)3 * 256, w.hs);
+        st = lut_launch(3, 3, s, dst_pages(a, first), n, a.width, a.height, lut, (size_t)3 * 256, hs);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
@@ -480,7 +424,7 @@ int derived_table_run(const ToneImg& a, int mode, double param, int with_max, vo
 int gamma_oc(int channels) { return channels == 4 ? 3 : channels; }
 int clean_oc(int channels) { return channels == 1 ? 1 : 3; }
 
-int gamma_device(int channels, double k, double gamma, const ToneImg& a, void* stream)
+int gamma_device(int channels, double k, double gamma, const PageArgs& a, void* stream)
 {
     const bool ok = channels >= 1 && channels <= 4;
     const int st = tone_checks(a, ok, channels, ok ? gamma_oc(channels) : 0, true);
@@ -490,7 +434,7 @@ int gamma_device(int channels, double k, double gamma, const ToneImg& a, void* s
     return shared_table_run(a, channels, gamma_oc(channels), tab, false, stream);
 }
 
-int clean_device(int channels, const ToneImg& a, void* stream)
+int clean_device(int channels, const PageArgs& a, void* stream)
 {
     const bool ok = channels == 1 || channels == 3 || channels == 4;
     const int st = tone_checks(a, ok, channels, ok ? clean_oc(channels) : 0, true);
@@ -500,7 +444,7 @@ int clean_device(int channels, const ToneImg& a, void* stream)
     return shared_table_run(a, channels, clean_oc(channels), tab, true, stream);
 }
 
-int balance_device(int mode, double param, int with_max, const ToneImg& a, void* stream)
+int balance_device(int mode, double param, int with_max, const PageArgs& a, void* stream)
 {
     const int st = tone_checks(a, true, 3, 3, true);
     if (st != PRL_OK) return st;
@@ -512,14 +456,10 @@ template <typename Run>
 int tone_host(int channels, bool channels_ok, int oc, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
               size_t dst_step, Run&& run)
 {
-    const ToneImg a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
     const int st = tone_checks(a, channels_ok, channels, channels_ok ? oc : 0, false);
     if (st != PRL_OK) return st;
-    const size_t in_row = (size_t)width * channels, out_row = (size_t)width * oc;
-    return stage_host_page(src, src_step, in_row, height, dst, dst_step, out_row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return run(ToneImg{1, d_in, in_bytes, in_row, width, height, d_out, out_bytes, out_row}, s);
-                           });
+    return stage_host_pages(a, channels, oc, width, height, run);
 }
 
 }  // namespace
@@ -533,17 +473,19 @@ extern "C" {
 int prl_hip_histogram_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
                                    int height, uint32_t* d_hist, void* stream)
 {
-    const ToneImg a{n_pages, d_src, src_page_stride, src_step, width, height, nullptr, 0, 0};
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, nullptr, 0, 0};
     int st = tone_checks(a, channels >= 1 && channels <= 4, channels, 0, true);
     if (st != PRL_OK) return st;
     if (!d_hist) return PRL_ERR_BAD_ARG;
     if (n_pages == 0) return PRL_OK;
-    ToneWork w;
-    st = tone_device(&w, stream);
+    int dev;   // no workspace and no lock: the device check alone
+    st = current_device(&dev);
     if (st != PRL_OK) return st;
-    for (int first = 0; first < n_pages; first += kToneChunk) {
-        st = hist_launch(channels, src_pages(a, first), std::min(kToneChunk, n_pages - first), width, height,
-                         d_hist + (size_t)first * channels * 256, w.hs);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int chunk = stage_chunk(n_pages, 0, 0, kToneChunk);
+    for (int first = 0; first < n_pages; first += chunk) {
+        st = hist_launch(channels, src_pages(a, first), std::min(chunk, n_pages - first), width, height,
+                         d_hist + (size_t)first * channels * 256, hs);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
@@ -553,18 +495,20 @@ int prl_hip_lut_batch_device(int n_pages, int channels, const uint8_t* d_lut, si
                              size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
                              size_t dst_step, void* stream)
 {
-    const ToneImg a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
     const bool ok = channels >= 1 && channels <= 4;
     int st = tone_checks(a, ok, channels, ok ? channels : 0, true);
     if (st != PRL_OK) return st;
     if (!d_lut) return PRL_ERR_BAD_ARG;
     if (n_pages == 0) return PRL_OK;
-    ToneWork w;
-    st = tone_device(&w, stream);
+    int dev;   // no workspace and no lock: the device check alone
+    st = current_device(&dev);
     if (st != PRL_OK) return st;
-    for (int first = 0; first < n_pages; first += kToneChunk) {
-        st = lut_launch(channels, channels, src_pages(a, first), dst_pages(a, first), std::min(kToneChunk, n_pages - first), width, height,
-                        d_lut + (size_t)first * lut_page_stride, lut_page_stride, w.hs);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int chunk = stage_chunk(n_pages, 0, 0, kToneChunk);
+    for (int first = 0; first < n_pages; first += chunk) {
+        st = lut_launch(channels, channels, src_pages(a, first), dst_pages(a, first), std::min(chunk, n_pages - first), width, height,
+                        d_lut + (size_t)first * lut_page_stride, lut_page_stride, hs);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
@@ -574,7 +518,7 @@ int prl_hip_gamma_correction_batch_device(int n_pages, int channels, double k, d
                                           size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
                                           size_t dst_step, void* stream)
 {
-    return gamma_device(channels, k, gamma, ToneImg{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step},
+    return gamma_device(channels, k, gamma, PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step},
                         stream);
 }
 
@@ -582,7 +526,7 @@ int prl_hip_gamma_correction_host(int channels, double k, double gamma, const ui
                                   uint8_t* dst, size_t dst_step)
 {
     return tone_host(channels, channels >= 1 && channels <= 4, gamma_oc(channels), src, src_step, width, height, dst, dst_step,
-                     [&](const ToneImg& a, hipStream_t s) { return gamma_device(channels, k, gamma, a, s); });
+                     [&](const PageArgs& a, hipStream_t s) { return gamma_device(channels, k, gamma, a, s); });
 }
 
 int prl_hip_simple_white_balance_batch_device(int n_pages, double k, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
@@ -590,14 +534,14 @@ int prl_hip_simple_white_balance_batch_device(int n_pages, double k, const uint8
                                               void* stream)
 {
     return balance_device(kDeriveSimpleWhite, k, 0,
-                          ToneImg{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, stream);
+                          PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, stream);
 }
 
 int prl_hip_simple_white_balance_host(double k, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
                                       size_t dst_step)
 {
     return tone_host(3, true, 3, src, src_step, width, height, dst, dst_step,
-                     [&](const ToneImg& a, hipStream_t s) { return balance_device(kDeriveSimpleWhite, k, 0, a, s); });
+                     [&](const PageArgs& a, hipStream_t s) { return balance_device(kDeriveSimpleWhite, k, 0, a, s); });
 }
 
 int prl_hip_gray_world_batch_device(int n_pages, double p_norm, int with_max, const uint8_t* d_src, size_t src_page_stride,
@@ -605,20 +549,20 @@ int prl_hip_gray_world_batch_device(int n_pages, double p_norm, int with_max, co
                                     void* stream)
 {
     return balance_device(kDeriveGrayWorld1, p_norm, with_max != 0,
-                          ToneImg{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, stream);
+                          PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, stream);
 }
 
 int prl_hip_gray_world_host(double p_norm, int with_max, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
                             size_t dst_step)
 {
     return tone_host(3, true, 3, src, src_step, width, height, dst, dst_step,
-                     [&](const ToneImg& a, hipStream_t s) { return balance_device(kDeriveGrayWorld1, p_norm, with_max != 0, a, s); });
+                     [&](const PageArgs& a, hipStream_t s) { return balance_device(kDeriveGrayWorld1, p_norm, with_max != 0, a, s); });
 }
 
 int prl_hip_clean_background_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
                                           int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    return clean_device(channels, ToneImg{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step},
+    return clean_device(channels, PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step},
                         stream);
 }
 
@@ -626,7 +570,7 @@ int prl_hip_clean_background_host(int channels, const uint8_t* src, size_t src_s
                                   size_t dst_step)
 {
     return tone_host(channels, channels == 1 || channels == 3 || channels == 4, clean_oc(channels), src, src_step, width, height, dst,
-                     dst_step, [&](const ToneImg& a, hipStream_t s) { return clean_device(channels, a, s); });
+                     dst_step, [&](const PageArgs& a, hipStream_t s) { return clean_device(channels, a, s); });
 }
 
 int prl_hip_gamma_lut(double k, double gamma, uint8_t lut[256])
@@ -654,7 +598,7 @@ static int luts_pixels(const uint32_t* hist, int* pixels)
     for (int c = 0; c < 3; ++c)
         for (int v = 0; v < 256; ++v) total[c] += hist[c * 256 + v];
     if (total[0] == 0) return PRL_ERR_EMPTY;
-    if (total[1] != total[0] || total[2] != total[0] || total[0] > (unsigned long long)kToneMaxSide * kToneMaxSide) return PRL_ERR_BAD_ARG;
+    if (total[1] != total[0] || total[2] != total[0] || total[0] > (unsigned long long)kStageMaxSide * kStageMaxSide) return PRL_ERR_BAD_ARG;
     *pixels = (int)total[0];
     return PRL_OK;
 }

@@ -278,16 +278,17 @@ int bad_arg(const char* why)
     return PRL_ERR_BAD_ARG;
 }
 
-// The checks every entry shares, before any device is touched.
-int persp_checks(int n_pages, int channels, const void* per_page, const uint8_t* d_src, size_t src_step, int width, int height,
-                 const uint8_t* d_dst, const int32_t* out_wh, int border_mode)
+// The checks every entry shares, before any device is touched.  tables: the per-page arguments are all there; batch: a
+// *_batch_device entry, which never works in place.  The destination's rows are checked page by page against each result's own
+// size (fill_page), and there is no span check: the results' sizes differ.
+int persp_checks(const PageArgs& a, int channels, bool tables, int border_mode, bool batch)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    const int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (channels < 1 || channels > 4) return PRL_ERR_BAD_CHANNELS;
     if (border_mode != PRL_BORDER_CONSTANT && border_mode != PRL_BORDER_REPLICATE) return PRL_ERR_UNSUPPORTED;
-    if (n_pages < 0 || !per_page || !d_src || !d_dst || !out_wh || d_src == d_dst || src_step < (size_t)width * channels)
-        return PRL_ERR_BAD_ARG;
-    if (width > kMaxSide || height > kMaxSide) return bad_arg("warp: page sides above 32767");
+    if (pages_rows_ok(a, channels, 0, batch) != PRL_OK || !tables || !a.dst || (batch && a.src == a.dst)) return PRL_ERR_BAD_ARG;
+    if (pages_sides_ok(a, kMaxSide) != PRL_OK) return bad_arg("warp: page sides above 32767");
     return PRL_OK;
 }
 
@@ -317,33 +318,23 @@ BorderBytes border_bytes(const double* value)
 // The records go up through the device's shared workspace (pinned bounce block -> `small`) and the launches follow on the
 // caller's stream: nothing here waits for the device's work.  The host only waits until the previous call's copy has left
 // the bounce block before it overwrites it.
-int persp_run(int channels, std::vector<PerspPage>& pages, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
-              int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, int border_mode, const BorderBytes& cv, void* stream)
+int persp_run(int channels, const std::vector<PerspPage>& pages, const PageArgs& a, int border_mode, const BorderBytes& cv, void* stream)
 {
     const int n_pages = (int)pages.size();
     if (n_pages == 0) return PRL_OK;
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
     const size_t bytes = sizeof(PerspPage) * (size_t)n_pages;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    st = ensure_small(ctx, bytes);
+    WorkScope w;
+    int st = w.open(stream, 0, bytes, bytes);
     if (st != PRL_OK) return st;
-    st = ensure_pinned(ctx, bytes);
-    if (st != PRL_OK) return st;
-    ctx->lut_small[0] = ctx->lut_small[1] = nullptr;   // the block's head is overwritten
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
+    DeviceCtx* ctx = w.ctx;
+    const hipStream_t hs = w.stream;
     if (ctx->pinned_use) PRL_HIP_CHECK(hipEventSynchronize(ctx->pinned_use));
     else PRL_HIP_CHECK(hipEventCreateWithFlags(&ctx->pinned_use, hipEventDisableTiming));
     std::memcpy(ctx->pinned, pages.data(), bytes);
     PRL_HIP_CHECK(hipMemcpyAsync(ctx->small, ctx->pinned, bytes, hipMemcpyHostToDevice, hs));
     PRL_HIP_CHECK(hipEventRecord(ctx->pinned_use, hs));
-    const PerspPage* d_pp = static_cast<const PerspPage*>(ctx->small);
-    const int chunk = 65535;   // grid.z
+    const PerspPage* d_pp = w.small<const PerspPage>();
+    const int chunk = stage_chunk(n_pages, 0);   // grid.z
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
         int max_ow = 0, max_oh = 0;
@@ -351,14 +342,26 @@ int persp_run(int channels, std::vector<PerspPage>& pages, const uint8_t* d_src,
             max_ow = std::max(max_ow, pages[(size_t)(first + i)].ow);
             max_oh = std::max(max_oh, pages[(size_t)(first + i)].oh);
         }
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
+        const PageSet s = src_pages(a, first);
+        const PageSetOut d = dst_pages(a, first);
         st = border_mode == PRL_BORDER_REPLICATE
-                 ? launch_persp<PRL_BORDER_REPLICATE>(channels, s, d, width, height, cnt, max_ow, max_oh, d_pp + first, cv, hs)
-                 : launch_persp<PRL_BORDER_CONSTANT>(channels, s, d, width, height, cnt, max_ow, max_oh, d_pp + first, cv, hs);
+                 ? launch_persp<PRL_BORDER_REPLICATE>(channels, s, d, a.width, a.height, cnt, max_ow, max_oh, d_pp + first, cv, hs)
+                 : launch_persp<PRL_BORDER_CONSTANT>(channels, s, d, a.width, a.height, cnt, max_ow, max_oh, d_pp + first, cv, hs);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
+}
+
+// cv::warpPerspective of every page with its own matrix and result size (the checks have passed)
+int persp_pages(const PageArgs& a, int channels, const double* matrices, int inverse_map, const int32_t* out_wh, int border_mode,
+                const double* border_value, void* stream)
+{
+    std::vector<PerspPage> pages((size_t)a.n_pages);
+    for (int i = 0; i < a.n_pages; ++i) {
+        const int st = fill_page(matrices + 9 * (size_t)i, inverse_map, out_wh[2 * i], out_wh[2 * i + 1], channels, a.dst_step, &pages[(size_t)i]);
+        if (st != PRL_OK) return st;
+    }
+    return persp_run(channels, pages, a, border_mode, border_bytes(border_value), stream);
 }
 
 // size and matrix of one prl::warpCrop call (warp.cpp:42-68)
@@ -404,15 +407,10 @@ int prl_hip_warp_perspective_batch_device(int n_pages, int channels, const doubl
                                           size_t dst_page_stride, size_t dst_step, const int32_t* out_wh, int border_mode,
                                           const double* border_value, void* stream)
 {
-    int st = persp_checks(n_pages, channels, matrices, d_src, src_step, width, height, d_dst, out_wh, border_mode);
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    const int st = persp_checks(a, channels, matrices && out_wh, border_mode, true);
     if (st != PRL_OK) return st;
-    std::vector<PerspPage> pages((size_t)n_pages);
-    for (int i = 0; i < n_pages; ++i) {
-        st = fill_page(matrices + 9 * (size_t)i, inverse_map, out_wh[2 * i], out_wh[2 * i + 1], channels, dst_step, &pages[(size_t)i]);
-        if (st != PRL_OK) return st;
-    }
-    return persp_run(channels, pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step, border_mode,
-                     border_bytes(border_value), stream);
+    return persp_pages(a, channels, matrices, inverse_map, out_wh, border_mode, border_value, stream);
 }
 
 int prl_hip_warp_crop_batch_device(int n_pages, int channels, const int32_t* quads, double ratio, const uint8_t* d_src,
@@ -420,7 +418,8 @@ int prl_hip_warp_crop_batch_device(int n_pages, int channels, const int32_t* qua
                                    size_t dst_page_stride, size_t dst_step, int32_t* out_wh, int border_mode,
                                    const double* border_value, void* stream)
 {
-    int st = persp_checks(n_pages, channels, quads, d_src, src_step, width, height, d_dst, out_wh, border_mode);
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    int st = persp_checks(a, channels, quads && out_wh, border_mode, true);
     if (st != PRL_OK) return st;
     std::vector<PerspPage> pages((size_t)n_pages);
     std::vector<int32_t> wh(2 * (size_t)n_pages);
@@ -433,8 +432,7 @@ int prl_hip_warp_crop_batch_device(int n_pages, int channels, const int32_t* qua
         wh[2 * (size_t)i] = ow;
         wh[2 * (size_t)i + 1] = oh;
     }
-    st = persp_run(channels, pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step, border_mode,
-                   border_bytes(border_value), stream);
+    st = persp_run(channels, pages, a, border_mode, border_bytes(border_value), stream);
     if (st == PRL_OK) std::copy(wh.begin(), wh.end(), out_wh);
     return st;
 }
@@ -442,25 +440,21 @@ int prl_hip_warp_crop_batch_device(int n_pages, int channels, const int32_t* qua
 int prl_hip_warp_crop_host(int channels, const int32_t quad[8], double ratio, const uint8_t* src, size_t src_step, int width, int height,
                            uint8_t* dst, size_t dst_step, int border_mode, const double* border_value)
 {
-    if (width <= 0 || height <= 0 || !src) return PRL_ERR_EMPTY;
-    if (channels < 1 || channels > 4) return PRL_ERR_BAD_CHANNELS;
-    if (border_mode != PRL_BORDER_CONSTANT && border_mode != PRL_BORDER_REPLICATE) return PRL_ERR_UNSUPPORTED;
-    if (!quad || !dst || src_step < (size_t)width * channels) return PRL_ERR_BAD_ARG;
-    if (width > kMaxSide || height > kMaxSide) return bad_arg("warp: page sides above 32767");
+    if (!src) return PRL_ERR_EMPTY;   // a null image is an empty cv::Mat
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    int st = persp_checks(a, channels, quad != nullptr, border_mode, false);
+    if (st != PRL_OK) return st;
     int ow, oh;
     double M[9];
-    int st = crop_plan(quad, ratio, &ow, &oh, M);
+    st = crop_plan(quad, ratio, &ow, &oh, M);
     if (st != PRL_OK) return st;
     PerspPage probe;
     st = fill_page(M, 0, ow, oh, channels, dst_step, &probe);   // the matrix checks, before anything is copied
     if (st != PRL_OK) return st;
-    const size_t in_row = (size_t)width * channels, out_row = (size_t)ow * channels;
-    return stage_host_page(src, src_step, in_row, height, dst, dst_step, out_row, oh,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               const int32_t wh[2] = {ow, oh};
-                               return prl_hip_warp_perspective_batch_device(1, channels, M, 0, d_in, in_bytes, in_row, width, height, d_out,
-                                                                            out_bytes, out_row, wh, border_mode, border_value, s);
-                           });
+    return stage_host_pages(a, channels, channels, ow, oh, [&](const PageArgs& page, hipStream_t s) {
+        const int32_t wh[2] = {ow, oh};
+        return persp_pages(page, channels, M, 0, wh, border_mode, border_value, s);
+    });
 }
 
 }  // extern "C"

@@ -43,8 +43,7 @@ def rotate(pages, angles):
     mw, mh = max(s[0] for s in sizes), max(s[1] for s in sizes)
     buf = torch.empty((n, mh, mw, c), dtype=torch.uint8, device=t4.device)
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(t4.device.index or 0))
-    stream = torch.cuda.current_stream(t4.device).cuda_stream
+    stream = _capi.stream_on(t4)
     _capi.check(L.prl_hip_rotate_batch_device(n, c, ang.ctypes.data, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h,
                                               buf.data_ptr(), buf.stride(0), buf.stride(1), stream))
     outs = [buf[i, :oh, :ow] for i, (ow, oh) in enumerate(sizes)]
@@ -62,8 +61,7 @@ def deskew(pages):
     wh = np.zeros((n, 2), dtype=np.int32)
     ang = np.zeros(n, dtype=np.float64)
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(t4.device.index or 0))
-    stream = torch.cuda.current_stream(t4.device).cuda_stream
+    stream = _capi.stream_on(t4)
     _capi.check(L.prl_hip_deskew_batch_device(n, c, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h, buf.data_ptr(),
                                               buf.stride(0), buf.stride(1), wh.ctypes.data, ang.ctypes.data, stream))
     outs = [buf[i, : wh[i, 1], : wh[i, 0]] for i in range(n)]
@@ -83,8 +81,7 @@ def find_angle(pages, return_segments: bool = False):
     ang = np.zeros(n, dtype=np.float64)
     nseg = np.zeros(n, dtype=np.int32)
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(t.device.index or 0))
-    stream = torch.cuda.current_stream(t.device).cuda_stream
+    stream = _capi.stream_on(t)
     _capi.check(L.prl_hip_find_angle_batch_device(n, t.data_ptr(), t.stride(0), t.stride(1), w, h, ang.ctypes.data,
                                                   nseg.ctypes.data, stream))
     a = float(ang[0]) if single else ang
@@ -128,8 +125,7 @@ def houghp(image, threshold: int, line_length: int, line_gap: int) -> np.ndarray
         raise TypeError("expected an H x W uint8 CUDA tensor")
     h, w = image.shape
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(image.device.index or 0))
-    stream = torch.cuda.current_stream(image.device).cuda_stream
+    stream = _capi.stream_on(image)
     cap = 4096
     while True:
         lines = np.empty((cap, 4), dtype=np.int32)

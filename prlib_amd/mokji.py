@@ -19,58 +19,16 @@ import ctypes as C
 
 import numpy as np
 
-from . import _capi
-
-
-def _pages4(t):
-    import torch
-
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in (2, 3, 4):
-        raise TypeError("expected a uint8 CUDA tensor [N,] H x W [x C] or a numpy uint8 array")
-    if t.dim() == 2:
-        t4, oshape = t[None, :, :, None], tuple(t.shape)
-    elif t.dim() == 3 and t.shape[-1] <= 4:
-        t4, oshape = t[None], tuple(t.shape[:2])
-    elif t.dim() == 3:
-        t4, oshape = t[:, :, :, None], tuple(t.shape)
-    else:
-        t4, oshape = t, tuple(t.shape[:3])
-    c = t4.shape[3]
-    if t4.stride(3) != 1 and c > 1 or t4.stride(2) != c:
-        t4 = t4.contiguous()
-    return t4, oshape
+from . import _capi, _pages
 
 
 def binarizeMokji(pages, maxEdgeWidth=3, minEdgeMagnitude=20, out=None):
     """prl::binarizeMokji: 255 where gray is above the page's co-occurrence threshold, else 0."""
     L = _capi.lib()
     e, m = int(maxEdgeWidth), int(minEdgeMagnitude)
-    if isinstance(pages, np.ndarray):
-        if pages.dtype != np.uint8 or pages.ndim not in (2, 3):
-            raise TypeError("expected an H x W [x C] uint8 array")
-        img = pages if pages.ndim == 3 else pages[:, :, None]
-        if img.strides[2] != 1 or img.strides[1] != img.shape[2] or img.strides[0] < 0:
-            img = np.ascontiguousarray(img)
-        h, w, c = img.shape
-        res = np.empty((h, w), np.uint8) if out is None else out
-        if not isinstance(res, np.ndarray) or res.shape != (h, w) or res.dtype != np.uint8 or not res.flags.c_contiguous:
-            raise TypeError("out must be a C-contiguous H x W uint8 array")
-        _capi.check(L.prl_hip_binarize_mokji_host(c, e, m, img.ctypes.data, img.strides[0], w, h, res.ctypes.data, res.strides[0]))
-        return res
-    import torch
-
-    t4, oshape = _pages4(pages)
-    n, h, w, c = t4.shape
-    res = torch.empty(oshape, dtype=torch.uint8, device=pages.device) if out is None else out
-    if not isinstance(res, torch.Tensor) or tuple(res.shape) != oshape or res.dtype != torch.uint8 or res.device != pages.device \
-            or res.stride(-1) != 1:
-        raise TypeError("out must be a uint8 tensor [N,] H x W on the input's device, pixels dense")
-    r3 = res if res.dim() == 3 else res[None]
-    _capi.check(L.prl_hip_set_device(pages.device.index or 0))
-    stream = torch.cuda.current_stream(pages.device).cuda_stream
-    _capi.check(L.prl_hip_binarize_mokji_batch_device(n, c, e, m, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h, r3.data_ptr(),
-                                                      r3.stride(0), r3.stride(1), stream))
-    return res
+    return _pages.run(pages, _pages.same,
+                      lambda c, *a: L.prl_hip_binarize_mokji_host(c, e, m, *a),
+                      lambda n, c, *a: L.prl_hip_binarize_mokji_batch_device(n, c, e, m, *a), out, drop_channel=True)
 
 
 def mokjiThresholds(pages, maxEdgeWidth=3, minEdgeMagnitude=20, out=None):
@@ -79,17 +37,15 @@ def mokjiThresholds(pages, maxEdgeWidth=3, minEdgeMagnitude=20, out=None):
     import torch
 
     L = _capi.lib()
-    t4, oshape = _pages4(pages)
+    t4, _, batch = _pages.pages4(pages)
     n, h, w, c = t4.shape
-    tshape = oshape[:-2]
+    tshape = (n,) if batch else ()
     res = torch.empty(tshape, dtype=torch.int32, device=pages.device) if out is None else out
     if not isinstance(res, torch.Tensor) or tuple(res.shape) != tshape or res.dtype != torch.int32 or res.device != pages.device \
             or not res.is_contiguous():
         raise TypeError("out must be a contiguous int32 tensor [N] on the input's device")
-    _capi.check(L.prl_hip_set_device(pages.device.index or 0))
-    stream = torch.cuda.current_stream(pages.device).cuda_stream
     _capi.check(L.prl_hip_mokji_thresholds_batch_device(n, c, int(maxEdgeWidth), int(minEdgeMagnitude), t4.data_ptr(), t4.stride(0),
-                                                        t4.stride(1), w, h, res.data_ptr(), stream))
+                                                        t4.stride(1), w, h, res.data_ptr(), _capi.stream_on(pages)))
     return res
 
 
@@ -100,26 +56,17 @@ def cooccurrence(a, b, border=0, min_diff=0, out=None):
     import torch
 
     L = _capi.lib()
-    for t in (a, b):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or not t.is_cuda or t.dim() not in (2, 3):
-            raise TypeError("expected two uint8 CUDA tensors [N,] H x W")
+    a4, b4 = _pages.pages4(a, gray_only=True)[0], _pages.pages4(b, gray_only=True)[0]
     if a.shape != b.shape or a.device != b.device:
         raise TypeError("a and b must have the same shape and device")
-    a3, b3 = (a, b) if a.dim() == 3 else (a[None], b[None])
-    if a3.stride(2) != 1:
-        a3 = a3.contiguous()
-    if b3.stride(2) != 1:
-        b3 = b3.contiguous()
-    n, h, w = a3.shape
+    n, h, w, _ = a4.shape
     oshape = tuple(a.shape[:-2]) + (256, 256)
     res = torch.empty(oshape, dtype=torch.int32, device=a.device) if out is None else out
     if not isinstance(res, torch.Tensor) or tuple(res.shape) != oshape or res.dtype != torch.int32 or res.device != a.device \
             or not res.is_contiguous():
         raise TypeError("out must be a contiguous int32 tensor [N,] 256 x 256 on the input's device")
-    _capi.check(L.prl_hip_set_device(a.device.index or 0))
-    stream = torch.cuda.current_stream(a.device).cuda_stream
-    _capi.check(L.prl_hip_cooccurrence_batch_device(n, int(border), int(min_diff), a3.data_ptr(), a3.stride(0), a3.stride(1),
-                                                    b3.data_ptr(), b3.stride(0), b3.stride(1), w, h, res.data_ptr(), stream))
+    _capi.check(L.prl_hip_cooccurrence_batch_device(n, int(border), int(min_diff), a4.data_ptr(), a4.stride(0), a4.stride(1),
+                                                    b4.data_ptr(), b4.stride(0), b4.stride(1), w, h, res.data_ptr(), _capi.stream_on(a)))
     return res
 
 

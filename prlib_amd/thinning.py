@@ -41,8 +41,7 @@ def _thin(image, method: int, out=None):
         out = out.unsqueeze(0)
     if out.shape != t.shape or out.stride(2) != 1:
         raise ValueError("output tensor has the wrong shape")
-    _capi.check(L.prl_hip_set_device(t.device.index or 0))
-    stream = torch.cuda.current_stream(t.device).cuda_stream
+    stream = _capi.stream_on(t)
     _capi.check(L.prl_hip_thin_batch_device(method, n, t.data_ptr(), t.stride(0), t.stride(1), w, h,
                                             out.data_ptr(), out.stride(0), out.stride(1), stream))
     return out[0] if squeeze else out

@@ -83,11 +83,8 @@ def warp_perspective(pages, matrices, sizes, inverse_map: bool = False, border_m
         return []
     buf = _destination(t4, [(max(1, int(a)), max(1, int(b))) for a, b in wh], out)
     bv = _border(border_value)
-    import torch
-
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(t4.device.index or 0))
-    stream = torch.cuda.current_stream(t4.device).cuda_stream
+    stream = _capi.stream_on(t4)
     _capi.check(L.prl_hip_warp_perspective_batch_device(n, c, m.ctypes.data, 1 if inverse_map else 0, t4.data_ptr(), t4.stride(0),
                                                         t4.stride(1), w, h, buf.data_ptr(), buf.stride(0), buf.stride(1),
                                                         wh.ctypes.data, int(border_mode), bv.ctypes.data, stream))
@@ -106,11 +103,8 @@ def warp_crop(pages, quads, ratio: float = -1.0, border_mode: int = BORDER_CONST
     buf = _destination(t4, sizes, out)
     wh = np.zeros((n, 2), dtype=np.int32)
     bv = _border(border_value)
-    import torch
-
     L = _capi.lib()
-    _capi.check(L.prl_hip_set_device(t4.device.index or 0))
-    stream = torch.cuda.current_stream(t4.device).cuda_stream
+    stream = _capi.stream_on(t4)
     _capi.check(L.prl_hip_warp_crop_batch_device(n, c, q.ctypes.data, float(ratio), t4.data_ptr(), t4.stride(0), t4.stride(1), w, h,
                                                  buf.data_ptr(), buf.stride(0), buf.stride(1), wh.ctypes.data, int(border_mode),
                                                  bv.ctypes.data, stream))

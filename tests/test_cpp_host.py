@@ -81,6 +81,14 @@ def test_chain_schedule():
     assert r.returncode == 0 and "chain_schedule: OK" in r.stdout, r.stdout + r.stderr
 
 
+def test_page_args():
+    """prlib_amd/csrc/page_args.h (what the stage entries share: the overlap and in-place rule, the span of a batch, the pointer /
+    step / side checks, pages per chunk) against cases worked out by hand (plain C++, no device)."""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "test_page_args"], check=True)
+    r = subprocess.run([os.path.join(os.path.join(ROOT, "tests", "cpp"), "test_page_args")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "page_args: OK" in r.stdout, r.stdout + r.stderr
+
+
 def test_cpp_boundary_compiles_against_opencv_signatures():
     """The OpenCV-present branch of the C++ boundary (prl.h: PRL_HAVE_OPENCV).  No box of this pool has OpenCV, so that
     branch is compiled - syntax only - against tests/cpp/opencv_api/: declaration-only headers carrying OpenCV's real

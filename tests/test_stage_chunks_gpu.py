@@ -1,0 +1,98 @@
+"""The stage entries with more than one chunk of pages.  A second chunk normally needs 65 536 pages or 4 GiB of scratch; the
+hooks build's PRL_HIP_STAGE_CHUNK=2 caps every entry's chunk (stage_chunk, prl_internal.h), so five small pages run as 2, 2, 1
+and the per-chunk offsets of every entry - pages, thresholds, histograms, tables, page records - are exercised."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_five_pages_in_chunks_of_two(prl, cuda_device):
+    """Every batched result is byte for byte the stack of the five single-page calls of the same process (one page is one chunk
+    whatever the knob says); median, removeLines and the tone functions also equal their restatements.  All outputs are
+    integers: zero differing bytes, no tolerance."""
+    code = r'''
+import sys, numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+from prlib_amd import _capi
+_capi.use_library(_capi.HOOKS_LIB_PATH)
+import torch, prlib_amd as P, median_ref, lines_ref, tone_ref
+from prlib_amd import morphology as M
+
+N, H, W = 5, 80, 64    # the smallest page removeLines takes (its elements are W / 50 and H / 50 long)
+rng = np.random.default_rng(9)
+
+def cut(c):
+    """five pages out of a larger buffer: page stride and step exceed the dense ones; random content and a few ruled lines"""
+    buf = rng.integers(0, 256, size=(N, H + 16, W + 16) + ((c,) if c > 1 else ()), dtype=np.uint8)
+    for i in range(N):
+        buf[i, 3 + 10 + 7 * i, 5:5 + W] = 10 + i      # a horizontal rule, another row on every page
+        buf[i, 3:3 + H, 5 + 20 + 5 * i] = 20 + i      # a vertical rule
+        buf[i, 3 + 60 - 3 * i, 5 + 4:5 + W - 4] = 0
+    t = torch.from_numpy(buf).cuda()[:, 3:3 + H, 5:5 + W]
+    assert t.stride(0) > H * W * c and t.stride(1) > W * c
+    return t
+
+gray, colour = cut(1), cut(3)
+host = {1: gray.cpu().numpy(), 3: colour.cpu().numpy()}
+checked = []
+
+def same(name, batched, singles, ref=None):
+    """batched: N x ...; singles: the N results of the one-page calls; ref: the N pages of a restatement"""
+    got = batched.cpu().numpy()
+    want = np.stack([s.cpu().numpy() for s in singles])
+    assert got.shape == want.shape and got.dtype == want.dtype, (name, got.shape, want.shape)
+    assert np.array_equal(got, want), (name, "batched != single pages", int((got != want).sum()))
+    if ref is not None:
+        assert np.array_equal(got, np.stack(ref)), (name, "!= restatement", int((got != np.stack(ref)).sum()))
+    checked.append(name)
+
+def each(name, fn, channels, ref=None):
+    for c in channels:
+        pages = gray if c == 1 else colour
+        same("%s c=%d" % (name, c), fn(pages), [fn(pages[i]) for i in range(N)], None if ref is None else [ref(p) for p in host[c]])
+
+each("denoiseSaltPepper", lambda p: P.denoiseSaltPepper(p, 3, 2), (1, 3), lambda p: median_ref.denoise_salt_pepper(p, 3, 2))
+each("binarizeNativeAdaptive", lambda p: P.binarizeNativeAdaptive(p), (1, 3))
+each("binarizeAT", lambda p: P.binarizeAT(p, 5, 255, 19, 9), (3,))
+each("morphologyEx", lambda p: P.morphologyEx(p, M.MORPH_OPEN, M.MORPH_ELLIPSE, 5), (1, 3))
+each("correctNUIL", lambda p: P.correctNUIL(p, 7), (1, 3))
+each("removeLines", lambda p: P.removeLines(p), (1, 3), lines_ref.remove_lines)
+each("gammaCorrection", lambda p: P.gammaCorrection(p, 1.2, 0.8), (1, 3), lambda p: tone_ref.gamma_model(p, 1.2, 0.8))
+each("simpleWhiteBalance", lambda p: P.simpleWhiteBalance(p, 0.01), (3,), lambda p: tone_ref.swb_model(p, 0.01))
+each("grayWorld p=1", lambda p: P.grayWorldWhiteBalance(p, 1, False), (3,), lambda p: tone_ref.gw_model(p, 1.0, False))   # device tables
+each("grayWorld p=2", lambda p: P.grayWorldWhiteBalance(p, 2, False), (3,), lambda p: tone_ref.gw_model(p, 2.0, False))   # host tables
+each("cleanBackgroundToWhite", lambda p: P.cleanBackgroundToWhite(p), (1, 3))
+each("histogram", lambda p: P.histogram(p), (1, 3), lambda p: tone_ref.histograms(p).astype(np.int32))
+each("binarizeMokji", lambda p: P.binarizeMokji(p), (1, 3))
+each("mokjiThresholds", lambda p: P.mokjiThresholds(p), (1, 3))
+
+for c in (1, 3):   # a table set per page
+    pages = gray if c == 1 else colour
+    tables = rng.integers(0, 256, size=(N, c, 256), dtype=np.uint8)
+    td = torch.from_numpy(tables).cuda()
+    same("lut c=%d" % c, P.lut(pages, td), [P.lut(pages[i], td[i]) for i in range(N)], [tone_ref.apply_luts(host[c][i], tables[i]) for i in range(N)])
+
+quads = np.array([[3 + i, 4, 55 + i, 6 + i, 58, 70 - i, 5, 66 + i] for i in range(N)], dtype=np.int32)   # another quad on every page
+for c in (1, 3):
+    pages = gray if c == 1 else colour
+    got = P.warp_crop(pages, quads)
+    sizes = set()
+    for i in range(N):
+        one = P.warp_crop(pages[i:i + 1], quads[i])[0]
+        assert got[i].shape == one.shape and torch.equal(got[i], one), ("warp_crop", c, i)
+        sizes.add(tuple(one.shape[:2]))
+    assert len(sizes) > 1   # the pages' results differ in size
+    checked.append("warp_crop c=%d" % c)
+
+torch.cuda.synchronize()
+print("stage chunks ok: %d comparisons" % len(checked))
+'''
+    env = dict(os.environ, PRL_HIP_STAGE_CHUNK="2")
+    r = subprocess.run([sys.executable, "-c", code, ROOT], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "stage chunks ok" in r.stdout, r.stdout + r.stderr[-3000:]
