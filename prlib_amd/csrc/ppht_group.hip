@@ -42,12 +42,12 @@
 #include <cstring>
 #include <vector>
 
+#include "ppht_plan.h"
 #include "prl_internal.h"
 
 namespace prl_hip {
 namespace {
 
-constexpr int kNumAngle = 180;
 #ifndef PRL_GRP_THREADS
 #define PRL_GRP_THREADS 1024
 #endif
@@ -62,19 +62,11 @@ constexpr int kPostWave = 2;             // posts the next line's exchange while
 constexpr int kKeep = 32;               // chunks per direction whose points the first walk leaves for the second
 constexpr int kEraseWave0 = kGrpWaves > 4 ? kFetch / 64 : 1;   // the wavefronts that erase (wavefront 0 polls the mailboxes; with many wavefronts those that fetch mask bits are spared too)
 constexpr int kEraseWaves = kGrpWaves - kEraseWave0;
-constexpr int kMaxA = 180;              // angles per member (a small page is one member's)
-constexpr int kMaxG = 32;               // members per group
 constexpr unsigned kCellBias = 0x4000u; // a cell holds count + bias: neither half of a dword ever borrows from the other
 constexpr int kMboxSlots = 4;
 constexpr int kGranStride = 8;          // granules 64 bytes apart
 constexpr unsigned kAborted = 0xffffffffu;
-constexpr int kMaxSide = 8000;          // |count| <= 2 max(W, H) < bias
-
-struct GrpAngle {
-    float c, s;   // the trig table's entries of this angle
-    int base;     // cell index of r = 0 in this member's accumulator (may be negative: r starts at rmin)
-    int n;        // the angle
-};
+// (kNumAngle, kMaxA, kMaxG, kMaxSide and the GrpAngle layout: ppht_plan.h)
 
 struct GrpArgs {
     int width, height, threshold, line_length, line_gap;
@@ -750,56 +742,7 @@ __global__ void __launch_bounds__(kGrpThreads) k_ppht_group(GrpArgs a)
 
 }  // namespace
 
-// Geometry of the group kernel for W x H pages: members per group (0: the page does not qualify), angle tables.
-struct GroupPlan {
-    int G = 0;
-    std::vector<GrpAngle> tab;     // [G][kMaxA]
-    std::vector<int> tab_n, tab_dwords;
-    size_t lds_bytes = 0;          // dynamic LDS of the launch
-};
-
-static GroupPlan plan_group(int width, int height, int threshold, const float* ttab, size_t lds_budget, int min_g)
-{
-    GroupPlan gp;
-    if (std::max(width, height) > kMaxSide || threshold < 1) return gp;
-    // r = cvRound(x cos + y sin) over the page: between the projections of two opposite corners (float32 products and sum are
-    // monotone in x and y), widened by one cell against the float32 roundings
-    int rmin[kNumAngle], len[kNumAngle];
-    for (int n = 0; n < kNumAngle; ++n) {
-        const double c = ttab[2 * n], s = ttab[2 * n + 1];
-        const double x_lo = c >= 0 ? 0 : width - 1, x_hi = c >= 0 ? width - 1 : 0;
-        const double y_lo = s >= 0 ? 0 : height - 1, y_hi = s >= 0 ? height - 1 : 0;
-        rmin[n] = (int)std::floor(x_lo * c + y_lo * s) - 1;
-        const int rmax = (int)std::ceil(x_hi * c + y_hi * s) + 1;
-        len[n] = rmax - rmin[n] + 1;
-    }
-    for (int G = std::max(1, min_g); G <= kMaxG; ++G) {
-        if ((kNumAngle + G - 1) / G > kMaxA) continue;
-        size_t worst = 0;
-        for (int g = 0; g < G; ++g) {
-            size_t cells = 0;
-            for (int n = g; n < kNumAngle; n += G) cells += (size_t)len[n];
-            worst = std::max(worst, (cells + 1) / 2 * 4);
-        }
-        if (worst > lds_budget) continue;
-        gp.G = G;
-        gp.lds_bytes = worst;
-        gp.tab.assign((size_t)G * kMaxA, GrpAngle{0.f, 0.f, 0, 0});
-        gp.tab_n.assign((size_t)G, 0);
-        gp.tab_dwords.assign((size_t)G, 0);
-        for (int g = 0; g < G; ++g) {
-            int cells = 0, k = 0;
-            for (int n = g; n < kNumAngle; n += G, ++k) {
-                gp.tab[(size_t)g * kMaxA + k] = GrpAngle{ttab[2 * n], ttab[2 * n + 1], cells - rmin[n], n};
-                cells += len[n];
-            }
-            gp.tab_n[(size_t)g] = k;
-            gp.tab_dwords[(size_t)g] = (cells + 1) / 2;
-        }
-        return gp;
-    }
-    return gp;
-}
+// (GroupPlan / plan_group, the geometry of the launch: ppht_plan.h)
 
 bool ppht_group_eligible(int width, int height, int threshold)
 {

@@ -89,6 +89,16 @@ def test_page_args():
     assert r.returncode == 0 and "page_args: OK" in r.stdout, r.stdout + r.stderr
 
 
+def test_ppht_plan():
+    """prlib_amd/csrc/ppht_plan.h (the geometry of the HoughLinesP group kernel: members per group, the angles of each, the rows
+    of their cells): every cvRound(x cos + y sin) of a page falls in its angle's row, the rows of a member are disjoint and the
+    members cover each angle once, the group is the smallest that fits the LDS, for 51 page sizes and every requested group size
+    1..32 (plain C++, no device)."""
+    subprocess.run(["make", "-C", os.path.join(ROOT, "tests", "cpp"), "-s", "test_ppht_plan"], check=True)
+    r = subprocess.run([os.path.join(os.path.join(ROOT, "tests", "cpp"), "test_ppht_plan")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "ppht_plan: OK" in r.stdout, r.stdout + r.stderr
+
+
 def test_cpp_boundary_compiles_against_opencv_signatures():
     """The OpenCV-present branch of the C++ boundary (prl.h: PRL_HAVE_OPENCV).  No box of this pool has OpenCV, so that
     branch is compiled - syntax only - against tests/cpp/opencv_api/: declaration-only headers carrying OpenCV's real

@@ -1,0 +1,232 @@
+"""HoughLinesP's three kernels (k_ppht_group of ppht_group.hip; k_ppht_mw and k_ppht of deskew.hip) against the CPU oracle on the
+shared case list (tests/houghp_cases.py): every group size the plan can give, the page and point-count edges, several pages per
+group, the placement by XCD, the eligibility edges, a segment list smaller than the result, a strided view.  All comparisons are
+exact: same segments, same order.
+
+The tuning knobs (hooks build) are read once per process, so every knob setting runs in a fresh child process, one after another,
+each under a time limit of its own."""
+import ctypes as C
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import houghp_cases as hc
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CHILD_TIMEOUT = 120   # seconds: a few seconds of work and the torch import
+
+# Members per group the plan gives these pages when nothing asks for more (tests/cpp/test_ppht_plan.cpp pins 2, 7 and 12 for a
+# budget of 155 KB; the device's budget is 160 KB less the kernel's static state, below the 153 452 bytes a member of 12 needs
+# for 16 x 8000, which therefore runs with 13: the tests below ask for groups of 11 and 16, either side of both).
+NATURAL_G = {(97, 203): 1, (64, 160): 1, (300, 420): 2, (24, 4400): 7, (16, 8000): 12, (40, 50): 1, (61, 23): 1, (1, 300): 1, (70, 129): 1}
+
+_CHILD = r'''
+import sys
+root, mode = sys.argv[1], sys.argv[2]
+sys.path[:0] = [root, root + "/tests"]
+import ctypes as C
+import numpy as np, torch
+import prlib_amd
+prlib_amd._capi.use_library(prlib_amd._capi.HOOKS_LIB_PATH)   # the build that reads the PRL_HIP_* tuning knobs
+from oracle import capi as oc
+import houghp_cases as hc
+
+def note(s):
+    sys.stderr.write("[case] %s\n" % s); sys.stderr.flush()
+
+def first_diff(got, want):
+    for k in range(min(len(got), len(want))):
+        if not np.array_equal(got[k], want[k]): return k
+    return min(len(got), len(want))
+
+bad = 0
+if mode in ("cases", "edges"):
+    todo = hc.cases()
+    if mode == "edges":
+        frame, side = hc.case("frame")[1], hc.case("side8000")
+        todo = [("frame_thr15", frame, 15, 10, 1, 9), ("frame_thr16", frame, 16, 10, 1, 8),
+                ("side8001", hc.side_page(8001), 2000, 1000, 5, 2), side]
+    for name, img, thr, ll, gap, min_seg in todo:
+        note(name)
+        want = oc.houghp(img, thr, ll, gap)
+        got = prlib_amd.houghp(torch.from_numpy(img.copy()).cuda(), thr, ll, gap)
+        if len(want) < min_seg or not np.array_equal(got, want):
+            bad += 1
+            print("MISMATCH %s: %d segments, the oracle has %d (at least %d expected), first difference at %d"
+                  % (name, len(got), len(want), min_seg, first_diff(got, want)))
+elif mode == "batch":
+    from prlib_amd import synth
+    pages = []
+    for i, skew in enumerate((2.0, -3.5, 0.0, 7.0, -1.0, 4.5, 0.5, -6.0)):
+        pages.append(oc.otsu(synth.text_page_numpy(300, 420, 60 + i, skew_deg=skew))[1])
+    pages.append(np.full((300, 420), 255, np.uint8))                      # no point
+    one = np.full((300, 420), 255, np.uint8); one[150, 200] = 0           # a single point
+    pages.append(one)
+    rows = np.full((300, 420), 255, np.uint8); rows[10::20, :] = 0        # full dark rows every 20 lines
+    pages.append(rows)
+    rng = np.random.default_rng(11)
+    pages.append(np.where(rng.random((300, 420)) < 0.25, 0, 255).astype(np.uint8))   # a quarter of the pixels dark
+    batch = np.stack(pages)
+    want = [oc.find_angle(p) for p in pages]
+    want_d = [oc.deskew(p) for p in pages]
+    if sum(n > 5 for _, n in want) < 9 or sum(a != 0.0 for a, _ in want) < 5:
+        bad += 1
+        print("MISMATCH batch: the oracle finds too little:", want)
+    t = torch.from_numpy(batch).cuda()
+    for rnd in range(2):                                                  # the second call runs on warm workspaces
+        note("find_angle %d" % rnd)
+        ang, nseg = prlib_amd.findAngle(t, return_segments=True)
+        for i in range(len(pages)):
+            if ang[i] != want[i][0] or nseg[i] != want[i][1]:
+                bad += 1
+                print("MISMATCH round %d page %d: angle %r with %d segments, the oracle has %r with %d" % (rnd, i, ang[i], nseg[i], want[i][0], want[i][1]))
+        note("deskew %d" % rnd)
+        outs, angles = prlib_amd.deskew(t)
+        for i in range(len(pages)):
+            o = outs[i].cpu().numpy()
+            if angles[i] != want_d[i][1]["angle"] or o.shape != want_d[i][0].shape or not np.array_equal(o, want_d[i][0]):
+                bad += 1
+                print("MISMATCH round %d page %d: deskewed page differs (angle %r, the oracle has %r)" % (rnd, i, angles[i], want_d[i][1]["angle"]))
+elif mode == "cap":
+    name, img, thr, ll, gap, min_seg = hc.case("n1023")
+    note(name)
+    want = oc.houghp(img, thr, ll, gap)
+    t = torch.from_numpy(img.copy()).cuda()
+    lines = np.full((8, 4), -7, np.int32)
+    n = C.c_int(-1)
+    st = prlib_amd._capi.lib().prl_hip_houghp_device(t.data_ptr(), t.stride(0), 50, 40, thr, ll, gap, lines.ctypes.data, 3, C.byref(n), None)
+    torch.cuda.synchronize()
+    if st != 0 or n.value != 27 or len(want) != 27 or not np.array_equal(lines[:3], want[:3]) or not (lines[3:] == -7).all():
+        bad += 1
+        print("MISMATCH cap 3: status %d, %d segments, rows %r" % (st, n.value, lines.tolist()))
+print("BAD", bad)
+'''
+
+
+def _run_child(mode, extra_env):
+    env = dict(os.environ, PRL_HIP_DEBUG="1", **extra_env)
+    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, mode], capture_output=True, text=True, timeout=CHILD_TIMEOUT, env=env)
+    assert r.returncode == 0 and "BAD 0" in r.stdout.splitlines(), r.stdout[-3000:] + r.stderr[-3000:]
+    return r.stderr
+
+
+_GROUP_LINE = re.compile(r"\[prl ppht\] group kernel: (\d+) pages, (\d+) members per group, (\d+) groups, (\d+) workgroups, (\d+) bytes of LDS; (\d+) pages left to k_ppht_mw")
+
+
+def _per_case(err):
+    """stderr of a child -> {case: [(pages, members, groups, workgroups, lds bytes, pages left), ...]}, one tuple per run of the
+    group kernel while that case was being worked on."""
+    out, cur = {}, None
+    for ln in err.splitlines():
+        if ln.startswith("[case] "):
+            cur = ln[7:]
+            out[cur] = []
+        m = _GROUP_LINE.search(ln)
+        if m:
+            assert cur is not None, ln
+            out[cur].append(tuple(int(v) for v in m.groups()))
+    return out
+
+
+def _check_groups(err, g):
+    """Every case of the list went through the group kernel, with g members where the page needs no more (never fewer than it
+    needs), and no page was left to the kernel that redoes what a group gave up."""
+    runs = _per_case(err)
+    for name, img, *_ in hc.cases():
+        assert len(runs.get(name, [])) == 1, (name, runs.get(name), err[-2000:])
+        pages, members, groups, workgroups, lds, left = runs[name][0]
+        natural = NATURAL_G[img.shape]
+        assert members == g if natural <= g else members >= natural, (name, g, runs[name])
+        assert left == 0 and pages == 1 and groups == 1 and lds <= 160 * 1024, (name, runs[name])
+    return runs
+
+
+@pytest.mark.parametrize("g", [1, 2, 3, 5, 6, 7, 9, 11, 16, 32])
+def test_group_size(g):
+    """Groups of g workgroups (PRL_HIP_PPHT_GROUP_G: at least g members): up to 5 a wavefront owns more than kU angles and takes the
+    voting path fed from s_ang, from 6 on never; where g does not divide 180 the members hold unequal numbers of angles; at 32 ten
+    of a member's sixteen wavefronts own no angle and still take part in every ballot and barrier."""
+    err = _run_child("cases", {"PRL_HIP_PPHT_GROUP": "1", "PRL_HIP_PPHT_GROUP_G": str(g)})
+    _check_groups(err, g)
+
+
+def test_group_xcd_placement():
+    """PRL_HIP_PPHT_GROUP_XCD=1: the members of a group are the workgroups b, b + 8, b + 16 (one XCD); the grid is 8 G workgroups
+    of which those of the groups without a page leave at once."""
+    err = _run_child("cases", {"PRL_HIP_PPHT_GROUP": "1", "PRL_HIP_PPHT_GROUP_G": "3", "PRL_HIP_PPHT_GROUP_XCD": "1"})
+    for name, r in _check_groups(err, 3).items():
+        assert r[0][3] == 8 * r[0][1], (name, r)
+
+
+def test_groups_take_several_pages_each():
+    """Two groups of two (PRL_HIP_PPHT_GROUP_G=2 PRL_HIP_PPHT_GROUP_CUS=4) share twelve pages: the queue pop, the re-zeroing of
+    the cells and of the private masks, the mailbox sequence carried from page to page; findAngle and deskew, twice in one process
+    (the second call finds mailboxes, queue word and status of the first in its workspace)."""
+    err = _run_child("batch", {"PRL_HIP_PPHT_GROUP_G": "2", "PRL_HIP_PPHT_GROUP_CUS": "4"})
+    runs = _per_case(err)
+    assert sorted(runs) == ["deskew 0", "deskew 1", "find_angle 0", "find_angle 1"], err[-2000:]
+    for name, r in runs.items():
+        assert len(r) == 1 and r[0][:4] == (12, 2, 2, 4) and r[0][5] == 0, (name, r)
+
+
+def test_fallback_kernels_on_the_same_cases():
+    """k_ppht_mw (PRL_HIP_PPHT_GROUP=0) and k_ppht (PRL_HIP_PPHT_GROUP=0 PRL_HIP_PPHT_MW=0), the accumulator in device memory."""
+    for env in ({"PRL_HIP_PPHT_GROUP": "0"}, {"PRL_HIP_PPHT_GROUP": "0", "PRL_HIP_PPHT_MW": "0"}):
+        err = _run_child("cases", env)
+        assert "group kernel" not in err, (env, err[-2000:])
+        assert len(_per_case(err)) == len(hc.cases())
+
+
+def test_eligibility_edges():
+    """Default knobs: threshold 15 and a side of 8001 are not the group kernel's (k_ppht_mw: an accumulator of 180 x (2 (W + H) + 1)
+    ints), threshold 16 and a side of 8000 are."""
+    runs = _per_case(_run_child("edges", {}))
+    assert sorted(runs) == ["frame_thr15", "frame_thr16", "side8000", "side8001"]
+    assert runs["frame_thr15"] == [] and runs["side8001"] == [], runs
+    for name in ("frame_thr16", "side8000"):
+        assert len(runs[name]) == 1 and runs[name][0][5] == 0, runs
+    assert runs["frame_thr16"][0][1] == 1 and runs["side8000"][0][1] >= 12, runs
+
+
+def _capped(prl, oracle, cuda_device):
+    import torch
+
+    name, img, thr, ll, gap, _ = hc.case("n1023")
+    want = oracle.houghp(img, thr, ll, gap)
+    t = torch.from_numpy(img.copy()).to(cuda_device)
+    lines = np.full((8, 4), -7, np.int32)
+    n = C.c_int(-1)
+    st = prl._capi.lib().prl_hip_houghp_device(t.data_ptr(), t.stride(0), 50, 40, thr, ll, gap, lines.ctypes.data, 3, C.byref(n), None)
+    torch.cuda.synchronize()
+    return st, n.value, lines, want
+
+
+def test_segment_list_smaller_than_the_result(prl, oracle, cuda_device):
+    """prl_hip_houghp_device with room for 3 of 27 segments: the count is the whole result's, the first three are stored, the rows
+    behind them are not touched; the product library in this process, the two fallback kernels in a child each."""
+    st, n, lines, want = _capped(prl, oracle, cuda_device)
+    assert st == 0 and n == 27 and len(want) == 27
+    assert np.array_equal(lines[:3], want[:3]) and (lines[3:] == -7).all(), lines
+    for env in ({"PRL_HIP_PPHT_GROUP": "0"}, {"PRL_HIP_PPHT_GROUP": "0", "PRL_HIP_PPHT_MW": "0"}):
+        assert "group kernel" not in _run_child("cap", env)
+
+
+def test_points_outside_a_strided_view_are_not_points(prl, oracle, cuda_device):
+    """The frame case inside a wider tensor of 255s (rows 260 bytes apart, 3 columns and 2 rows in): the same segments."""
+    import torch
+
+    name, img, thr, ll, gap, min_seg = hc.case("frame")
+    want = oracle.houghp(img, thr, ll, gap)
+    assert len(want) >= min_seg
+    wide = torch.full((101, 260), 255, dtype=torch.uint8, device=cuda_device)
+    view = wide[2:99, 3:206]
+    view.copy_(torch.from_numpy(img.copy()))
+    assert view.stride(0) == 260 and not view.is_contiguous()
+    assert np.array_equal(prl.houghp(view, thr, ll, gap), want)
+    assert np.array_equal(prl.houghp(view.contiguous(), thr, ll, gap), want)
