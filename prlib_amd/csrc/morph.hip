@@ -638,9 +638,10 @@ __global__ void __launch_bounds__(256) k_morph_bits(PageSet src, PageSetOut dst,
     }
 }
 
-// launches k_morph_bits; PRL_ERR_BAD_ARG when the grid would not fit (the caller falls back)
+// launches k_morph_bits; PRL_ERR_BAD_ARG when the grid would not fit (the caller falls back).  rows_per_seg > 0 (the test-hooks
+// entry only) replaces the segment height chosen here.
 int launch_morph_bits(int iterations, bool bitsrc, const PageSet& src, int n_pages, int width, int height,
-                      const PageSetOut& dst, hipStream_t stream)
+                      const PageSetOut& dst, hipStream_t stream, int rows_per_seg = 0)
 {
     const int n = iterations > 0 ? iterations : -iterations;
     const int n_strips = (width + 15 + kBitsAdvance - 1) / kBitsAdvance;
@@ -648,6 +649,7 @@ int launch_morph_bits(int iterations, bool bitsrc, const PageSet& src, int n_pag
     // small batches: fill the chip first (one 4K page, closing 2: 0.082 -> 0.069 ms per call at 8 rows per segment)
     while (rps > 8 && (long long)n_pages * n_strips * ((height + rps - 1) / rps) < 16384) rps /= 2;
     if (env_knobs().morph_rps) rps = env_knobs().morph_rps;  // tuning knob
+    if (rows_per_seg > 0) rps = rows_per_seg;
     const int n_segs = (height + rps - 1) / rps;
     const unsigned long long tw = (unsigned long long)n_pages * n_strips * n_segs;
     if (tw >= 0xfffffff0ull) return PRL_ERR_BAD_ARG;
@@ -727,7 +729,7 @@ int morph_large_run(int iterations, const PageSet& src, int n_pages, int width, 
 
 // binary (0/255) masks: the pipeline's own threshold output
 int morph_binary_run(int iterations, const PageSet& src, int n_pages, int width, int height,
-                     const PageSetOut& dst, hipStream_t stream)
+                     const PageSetOut& dst, hipStream_t stream, int* kernel_run, int rows_per_seg)
 {
     const int n = iterations > 0 ? iterations : -iterations;
     if (n == 0 || n > kMaxN) {
@@ -738,7 +740,10 @@ int morph_binary_run(int iterations, const PageSet& src, int n_pages, int width,
         src.step >= (size_t)((width + 15) / 16) * 16) {
         // bit-domain streaming kernel: needs 16-byte aligned source rows padded to whole 16-pixel chunks (the
         // pipeline's own mask buffer always is)
-        if (launch_morph_bits(iterations, false, src, n_pages, width, height, dst, stream) == PRL_OK) return PRL_OK;
+        if (launch_morph_bits(iterations, false, src, n_pages, width, height, dst, stream, rows_per_seg) == PRL_OK) {
+            if (kernel_run) *kernel_run = kMorphRanBitsFromBytes;
+            return PRL_OK;
+        }
     }
     if ((((size_t)src.base | src.page_stride | src.step) & 3) == 0 && !src.table) {
         // streaming kernel: needs 4-byte aligned source rows (the pipeline's own mask buffer always is)
@@ -746,6 +751,7 @@ int morph_binary_run(int iterations, const PageSet& src, int n_pages, int width,
         const int n_strips = (width + useful - 1) / useful;
         int rps = 128;  // short segments: many wavefronts, each with two row fetches in flight
         while (rps > 32 && (long long)n_pages * n_strips * ((height + rps - 1) / rps) < 32768) rps /= 2;
+        if (rows_per_seg > 0) rps = rows_per_seg;
         const int n_segs = (height + rps - 1) / rps;
         const unsigned long long tw = (unsigned long long)n_pages * n_strips * n_segs;
         if (tw < 0xfffffff0ull) {
@@ -758,6 +764,7 @@ int morph_binary_run(int iterations, const PageSet& src, int n_pages, int width,
                 hipLaunchKernelGGL(k_morph_stream<false>, dim3(blocks), dim3(256), lds, stream, src, dst, width, height, n,
                                    n_strips, n_segs, rps, (unsigned)tw);
             PRL_HIP_CHECK(hipGetLastError());
+            if (kernel_run) *kernel_run = kMorphRanStream;
             return PRL_OK;
         }
     }
@@ -769,6 +776,7 @@ int morph_binary_run(int iterations, const PageSet& src, int n_pages, int width,
     else
         hipLaunchKernelGGL(k_morph_binary<false>, grid, dim3(256), 0, stream, src, dst, width, height, n, btw);
     PRL_HIP_CHECK(hipGetLastError());
+    if (kernel_run) *kernel_run = kMorphRanBinary;
     return PRL_OK;
 }
 
@@ -776,13 +784,15 @@ int morph_binary_run(int iterations, const PageSet& src, int n_pages, int width,
 int morph_bits_max_radius() { return kBitsMaxN; }
 
 int morph_bitplane_run(int iterations, const PageSet& bits, int n_pages, int width, int height, const PageSetOut& dst,
-                       hipStream_t stream)
+                       hipStream_t stream, int* kernel_run, int rows_per_seg)
 {
     const int n = iterations > 0 ? iterations : -iterations;
     if (n == 0 || n > kBitsMaxN || bits.table || (((size_t)bits.base | bits.page_stride | bits.step) & 1) != 0 ||
         bits.step < (size_t)((width + 15) / 16) * 2)
         return PRL_ERR_BAD_ARG;
-    return launch_morph_bits(iterations, true, bits, n_pages, width, height, dst, stream);
+    const int st = launch_morph_bits(iterations, true, bits, n_pages, width, height, dst, stream, rows_per_seg);
+    if (st == PRL_OK && kernel_run) *kernel_run = kMorphRanBitsFromBits;
+    return st;
 }
 
 int pack_mask_run(const uint8_t* src, size_t src_step, int width, int height, uint8_t* bits, size_t bit_step,
@@ -813,3 +823,39 @@ int morph_run(int iterations, const PageSet& src, int n_pages, int width, int he
 }
 
 }  // namespace prl_hip
+
+#ifdef PRL_TEST_HOOKS
+extern "C" {
+
+// libprlib_hip_testhooks.so only: the mask morphology of the binarizers on a caller's mask, through the product's own dispatch
+// (morph_from_mask in prl_capi.hip makes the same two calls).  form 0: d_src is a byte mask (0 / 255) and the kernel follows from
+// its alignment and the radius (morph_binary_run); form 1: d_src is a bit plane (pixel x = bit x & 7 of byte x >> 3,
+// morph_bitplane_run).  *kernel_run receives the kMorphRan* value of the kernel that was launched (0: none); rows_per_seg > 0
+// replaces the segment height of k_morph_bits / k_morph_stream for this call.
+int prl_hip_internal_mask_morph(int form, int iterations, int rows_per_seg, int n_pages, const uint8_t* d_src, size_t src_page_stride,
+                                size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                int* kernel_run, void* stream)
+{
+    using namespace prl_hip;
+    if (kernel_run) *kernel_run = 0;
+    if ((form != 0 && form != 1) || rows_per_seg < 0 || n_pages <= 0 || width <= 0 || height <= 0 || !d_src || !d_dst ||
+        dst_step < (size_t)width || (form == 0 && src_step < (size_t)width))
+        return PRL_ERR_BAD_ARG;
+    const PageSet src = page_set(d_src, src_page_stride, src_step);
+    const PageSetOut dst = page_set_out(d_dst, dst_page_stride, dst_step);
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    if (form == 1) return morph_bitplane_run(iterations, src, n_pages, width, height, dst, hs, kernel_run, rows_per_seg);
+    return morph_binary_run(iterations, src, n_pages, width, height, dst, hs, kernel_run, rows_per_seg);
+}
+
+// k_pack_mask: a byte mask (bit 0 of every byte counts) -> the bit plane of form 1; bit_step >= ceil(width / 8)
+int prl_hip_internal_pack_mask(const uint8_t* d_src, size_t src_step, int width, int height, uint8_t* d_bits, size_t bit_step,
+                               void* stream)
+{
+    if (width <= 0 || height <= 0 || !d_src || !d_bits || src_step < (size_t)width || bit_step < (size_t)((width + 7) / 8))
+        return PRL_ERR_BAD_ARG;
+    return prl_hip::pack_mask_run(d_src, src_step, width, height, d_bits, bit_step, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"
+#endif

@@ -473,14 +473,17 @@ int gmorph_dilate_rect_run(int k, int width, int height, const PageSet& src, con
 // ---- morphology (morph.hip) ------------------------------------------------------------------
 int morph_run(int iterations, const PageSet& src, int n_pages, int width, int height,
               const PageSetOut& dst, hipStream_t stream);
+// kernel_run (optional) receives which kernel was launched; rows_per_seg > 0 replaces the segment height of the two streaming
+// kernels (both for the prl_hip_internal_mask_morph entry of the test-hooks build: product calls leave them out)
+enum { kMorphRanBitsFromBytes = 1, kMorphRanBitsFromBits = 2, kMorphRanStream = 3, kMorphRanBinary = 4 };
 int morph_binary_run(int iterations, const PageSet& src, int n_pages, int width, int height,
-                     const PageSetOut& dst, hipStream_t stream);
+                     const PageSetOut& dst, hipStream_t stream, int* kernel_run = nullptr, int rows_per_seg = 0);
 int morph_large_run(int iterations, const PageSet& src, int n_pages, int width, int height, const PageSetOut& dst,
                     uint8_t* tmp, size_t tmp_step, hipStream_t stream);
 int morph_bits_max_radius();
 // source = bit plane (rows of bits.step bytes, 1 bit per pixel, bit j of byte i = pixel 8 i + j)
 int morph_bitplane_run(int iterations, const PageSet& bits, int n_pages, int width, int height, const PageSetOut& dst,
-                       hipStream_t stream);
+                       hipStream_t stream, int* kernel_run = nullptr, int rows_per_seg = 0);
 int pack_mask_run(const uint8_t* src, size_t src_step, int width, int height, uint8_t* bits, size_t bit_step,
                   hipStream_t stream);
 constexpr int kMorphMaxFusedRadius = 8;  // morph_run / morph_binary_run handle |iterations| up to this

@@ -213,7 +213,7 @@ def test_product_does_not_reference_the_oracle():
 
 def test_library_exports_exactly_the_header():
     """libprlib_hip.so exports the functions include/prl_hip.h declares and nothing else (the reference marks exactly its public
-    functions CV_EXPORTS: binarizeSauvola.h:43); the test-hooks build adds the five prl_hip_internal_* entries; both carry the ABI
+    functions CV_EXPORTS: binarizeSauvola.h:43); the test-hooks build adds the seven prl_hip_internal_* entries; both carry the ABI
     version in their SONAME.  The linker maps are generated from the header (tools/gen_export_map.py)."""
     import shutil
     import subprocess
