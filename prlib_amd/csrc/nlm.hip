@@ -180,7 +180,10 @@ __device__ __forceinline__ void nlm_y_body(const PageSet& src, const PageSetOut&
     // a round trip then takes tens of microseconds, and the eight dependent batches the plain loop compiled to doubled the
     // kernel's time.)
     {
-        using Px = typename std::conditional<CH == 1, uint8_t, unsigned short>::type;   // 2 channels: aligned 16-bit pixels
+        // 2 channels: a pixel is 16 bits in LDS (aligned there), but two byte loads from memory - a caller's view may start at an
+        // odd address or have an odd row step, and the page pointer is generic (flat loads), so nothing promises an unaligned
+        // 16-bit load
+        using Px = typename std::conditional<CH == 1, uint8_t, unsigned short>::type;
         static_assert(CH <= 2, "k_nlm_y filters the L and the ab plane");
         constexpr int kIt = (EXT_H * EXT_W + 255) / 256;
         Px px[kIt];
@@ -191,7 +194,9 @@ __device__ __forceinline__ void nlm_y_body(const PageSet& src, const PageSetOut&
             if (i < EXT_H * EXT_W) {
                 const int r = i / EXT_W, c = i - r * EXT_W;
                 const int sy = reflect101(y0 - kBorder + r, H), sx = reflect101(x0 - kBorder + c, W);
-                px[it] = *reinterpret_cast<const Px*>(img + (size_t)sy * src.step + (size_t)sx * CH);
+                const uint8_t* p = img + (size_t)sy * src.step + (size_t)sx * CH;
+                if constexpr (CH == 1) px[it] = p[0];
+                else px[it] = (Px)(p[0] | (p[1] << 8));
             }
         }
         for (int i = threadIdx.x; i < EXT_H * (RAWP - EXT_W * CH); i += blockDim.x) {
@@ -728,6 +733,23 @@ const HostLab& host_lab()
 // Device copies of the LUT(s) / cbrt table live in the small workspace: [lutA 512 KiB][lutB 512 KiB][cbrt 8 KiB]
 constexpr size_t kLutSlot = 512 * 1024;
 
+// The table a call uploads: the leading entries that may be non-zero plus one closing zero (weights are non-increasing, so the
+// trailing zeros collapse into it).  *n_lut is set either way; a table that does not fit its workspace slot is refused.
+int trimmed_weights(int channels, float h, std::vector<int>* lut, int* n_lut)
+{
+    *lut = build_weights(channels, h);
+    int n = (int)lut->size();
+    while (n > 0 && (*lut)[(size_t)n - 1] == 0) --n;
+    lut->resize((size_t)n + 1);
+    (*lut)[(size_t)n] = 0;
+    *n_lut = n;
+    if ((size_t)(n + 1) * sizeof(int) > kLutSlot) {
+        set_error_detail("NLM weight table too large for the workspace (h too large)");
+        return PRL_ERR_BAD_ARG;
+    }
+    return PRL_OK;
+}
+
 int upload_lut(DeviceCtx* ctx, int slot, int channels, float h, hipStream_t stream, NlmParams* np)
 {
     int* dcached = reinterpret_cast<int*>(static_cast<uint8_t*>(ctx->small) + (size_t)slot * kLutSlot);
@@ -736,15 +758,10 @@ int upload_lut(DeviceCtx* ctx, int slot, int channels, float h, hipStream_t stre
         np->lut = dcached;             // 50-100 thousand exp() calls on the host, a visible share of a single page)
         return PRL_OK;
     }
-    std::vector<int> lut = build_weights(channels, h);
-    int n = (int)lut.size();
-    while (n > 0 && lut[(size_t)n - 1] == 0) --n;  // weights are non-increasing: trailing zeros collapse
-    lut.resize((size_t)n + 1);
-    lut[(size_t)n] = 0;
-    if ((size_t)(n + 1) * sizeof(int) > kLutSlot) {
-        set_error_detail("NLM weight table too large for the workspace (h too large)");
-        return PRL_ERR_BAD_ARG;
-    }
+    std::vector<int> lut;
+    int n = 0;
+    const int st = trimmed_weights(channels, h, &lut, &n);
+    if (st != PRL_OK) return st;
     int* d = reinterpret_cast<int*>(static_cast<uint8_t*>(ctx->small) + (size_t)slot * kLutSlot);
     // pageable source: hipMemcpyAsync stages it before returning, so `lut` may die after this call
     PRL_HIP_CHECK(hipMemcpyAsync(d, lut.data(), (size_t)(n + 1) * sizeof(int), hipMemcpyHostToDevice, stream));
@@ -758,10 +775,34 @@ int upload_lut(DeviceCtx* ctx, int slot, int channels, float h, hipStream_t stre
     return PRL_OK;
 }
 
-template <int CH>
-int launch_nlm(const PageSet& src_all, const PageSetOut& dst_all, int n_pages, const NlmParams& np, hipStream_t stream)
+// Which instantiation filters `channels` interleaved planes with a table of n_lut leading non-zero entries.  knob_xl bit 0 / 1:
+// the L / ab plane may take the 4-byte-element kernel; knob_glut bit 0 / 1: that kernel reads the table from memory (env_knobs():
+// 3 and 0 in the product library).
+enum NlmVariant { kNlmXlLds = 0, kNlmXlMem = 1, kNlmYLds = 2, kNlmYMem = 3, kNlm3Lds = 4, kNlm3Mem = 5, kNlmVariants = 6 };
+
+int nlm_variant(int channels, int n_lut, int knob_xl, int knob_glut)
 {
-    const bool lds_lut = np.n_lut <= kLutMax;
+    const bool lds_lut = n_lut <= kLutMax;
+    if (channels > 2) return lds_lut ? kNlm3Lds : kNlm3Mem;
+    const bool xl = n_lut <= kLutMaxXL && ((knob_xl >> (channels - 1)) & 1);
+    const bool glut = (knob_glut >> (channels - 1)) & 1;  // weight table from memory (L1) instead of LDS
+    if (xl) return glut ? kNlmXlMem : kNlmXlLds;
+    return lds_lut ? kNlmYLds : kNlmYMem;
+}
+
+// does the variant exist for this channel count, and does the table fit its LDS copy (if it keeps one)
+bool nlm_variant_fits(int variant, int channels, int n_lut)
+{
+    if (channels <= 2 ? (variant < kNlmXlLds || variant > kNlmYMem) : (variant != kNlm3Lds && variant != kNlm3Mem)) return false;
+    if (variant == kNlmXlLds) return n_lut <= kLutMaxXL;
+    if (variant == kNlmYLds || variant == kNlm3Lds) return n_lut <= kLutMax;
+    return true;
+}
+
+template <int CH>
+int launch_nlm(int variant, const PageSet& src_all, const PageSetOut& dst_all, int n_pages, const NlmParams& np, hipStream_t stream)
+{
+    if (!nlm_variant_fits(variant, CH, np.n_lut)) return PRL_ERR_BAD_ARG;
     if ((np.height + TILE_H - 1) / TILE_H > 65535) return PRL_ERR_BAD_ARG;  // grid.y
     for (int first = 0; first < n_pages; first += 65535) {  // grid.z holds at most 65535 pages per launch
         const int cnt = std::min(65535, n_pages - first);
@@ -772,16 +813,13 @@ int launch_nlm(const PageSet& src_all, const PageSetOut& dst_all, int n_pages, c
         const dim3 grid((np.width + TILE_W - 1) / TILE_W, (np.height + TILE_H - 1) / TILE_H, cnt);
         if (CH <= 2) {
             constexpr int C = CH <= 2 ? CH : 1;
-            const int xl_env = env_knobs().nlm_xl;
-            const bool xl = np.n_lut <= kLutMaxXL && ((xl_env >> (C - 1)) & 1);
-            const bool glut = (env_knobs().nlm_glut >> (C - 1)) & 1;  // weight table from memory (L1) instead of LDS
-            if (xl && glut) hipLaunchKernelGGL((k_nlm_y_xl<C, false>), grid, dim3(256), 0, stream, src, dst, np);
-            else if (xl) hipLaunchKernelGGL((k_nlm_y_xl<C, true>), grid, dim3(256), 0, stream, src, dst, np);
-            else if (lds_lut) hipLaunchKernelGGL((k_nlm_y<C, true>), grid, dim3(256), 0, stream, src, dst, np);
+            if (variant == kNlmXlMem) hipLaunchKernelGGL((k_nlm_y_xl<C, false>), grid, dim3(256), 0, stream, src, dst, np);
+            else if (variant == kNlmXlLds) hipLaunchKernelGGL((k_nlm_y_xl<C, true>), grid, dim3(256), 0, stream, src, dst, np);
+            else if (variant == kNlmYLds) hipLaunchKernelGGL((k_nlm_y<C, true>), grid, dim3(256), 0, stream, src, dst, np);
             else hipLaunchKernelGGL((k_nlm_y<C, false>), grid, dim3(256), 0, stream, src, dst, np);
         } else {
             constexpr int C = CH > 2 ? CH : 3;
-            if (lds_lut) hipLaunchKernelGGL((k_nlm<C, true>), grid, dim3(256), 0, stream, src, dst, np);
+            if (variant == kNlm3Lds) hipLaunchKernelGGL((k_nlm<C, true>), grid, dim3(256), 0, stream, src, dst, np);
             else hipLaunchKernelGGL((k_nlm<C, false>), grid, dim3(256), 0, stream, src, dst, np);
         }
         PRL_HIP_CHECK(hipGetLastError());
@@ -789,19 +827,21 @@ int launch_nlm(const PageSet& src_all, const PageSetOut& dst_all, int n_pages, c
     return PRL_OK;
 }
 
+// variant < 0: the one nlm_variant picks (every product call); else exactly that instantiation (test-hooks entry)
 int nlm_planes_locked(DeviceCtx* ctx, int slot, int n_pages, int channels, float h, const PageSet& src, int width,
-                      int height, const PageSetOut& dst, hipStream_t stream)
+                      int height, const PageSetOut& dst, hipStream_t stream, int variant = -1)
 {
+    if (channels < 1 || channels > 3) return PRL_ERR_BAD_CHANNELS;
     NlmParams np{};
     np.width = width;
     np.height = height;
     int st = upload_lut(ctx, slot, channels, h, stream, &np);
     if (st != PRL_OK) return st;
+    if (variant < 0) variant = nlm_variant(channels, np.n_lut, env_knobs().nlm_xl, env_knobs().nlm_glut);
     switch (channels) {
-    case 1: return launch_nlm<1>(src, dst, n_pages, np, stream);
-    case 2: return launch_nlm<2>(src, dst, n_pages, np, stream);
-    case 3: return launch_nlm<3>(src, dst, n_pages, np, stream);
-    default: return PRL_ERR_BAD_CHANNELS;
+    case 1: return launch_nlm<1>(variant, src, dst, n_pages, np, stream);
+    case 2: return launch_nlm<2>(variant, src, dst, n_pages, np, stream);
+    default: return launch_nlm<3>(variant, src, dst, n_pages, np, stream);
     }
 }
 
@@ -909,11 +949,10 @@ int denoise_all_locked(DeviceCtx* ctx, int cnt, int channels, float strength, co
 
 using namespace prl_hip;
 
-extern "C" {
-
-int prl_hip_nlm_planes_device(int n_pages, int channels, float h, const uint8_t* d_src, size_t src_page_stride,
-                              size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
-                              size_t dst_step, void* stream)
+// prl_hip_nlm_planes_device; variant >= 0 (test-hooks entry): that instantiation instead of the one nlm_variant picks
+static int nlm_planes_entry(int variant, int n_pages, int channels, float h, const uint8_t* d_src, size_t src_page_stride,
+                            size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                            void* stream)
 {
     if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
     if (channels < 1 || channels > 3) return PRL_ERR_BAD_CHANNELS;
@@ -933,7 +972,17 @@ int prl_hip_nlm_planes_device(int n_pages, int channels, float h, const uint8_t*
     DeviceRelease release{ctx, s};
     const PageSet ps = page_set(d_src, src_page_stride, src_step);
     const PageSetOut pd = page_set_out(d_dst, dst_page_stride, dst_step);
-    return nlm_planes_locked(ctx, 0, n_pages, channels, h, ps, width, height, pd, s);
+    return nlm_planes_locked(ctx, 0, n_pages, channels, h, ps, width, height, pd, s, variant);
+}
+
+extern "C" {
+
+int prl_hip_nlm_planes_device(int n_pages, int channels, float h, const uint8_t* d_src, size_t src_page_stride,
+                              size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                              size_t dst_step, void* stream)
+{
+    return nlm_planes_entry(-1, n_pages, channels, h, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride,
+                            dst_step, stream);
 }
 
 int prl_hip_denoise_batch_device(int n_pages, int channels, float strength, const uint8_t* d_src,
@@ -986,3 +1035,70 @@ int prl_hip_denoise_host(int channels, float strength, const uint8_t* src, size_
 }
 
 }  // extern "C"
+
+#ifdef PRL_TEST_HOOKS
+extern "C" {
+
+// libprlib_hip_testhooks.so only.  Host only, no GPU call: the weight table a call with (channels, h) uploads - *n_lut leading
+// entries that may be non-zero, the first min(*n_lut, cap) of them copied to `lut` - and in *variant the instantiation
+// launch_nlm runs for it under the given knobs (nlm_variant: 0 / 1 the 4-byte-element kernel with the table in LDS / from memory,
+// 2 / 3 the 8-byte-element kernel likewise, 4 / 5 the 3-channel kernel; knob_xl = 3, knob_glut = 0 are the product's values).
+// PRL_ERR_BAD_ARG with both outputs set when the table does not fit its workspace slot (upload_lut refuses it the same way).
+int prl_hip_internal_nlm_plan(int channels, float h, int knob_xl, int knob_glut, int* n_lut, int* variant, int32_t* lut, int cap)
+{
+    if (channels < 1 || channels > 3) return PRL_ERR_BAD_CHANNELS;
+    if (!n_lut || !variant || cap < 0 || (cap > 0 && !lut)) return PRL_ERR_BAD_ARG;
+    std::vector<int> t;
+    const int st = trimmed_weights(channels, h, &t, n_lut);
+    *variant = nlm_variant(channels, *n_lut, knob_xl, knob_glut);
+    std::copy(t.begin(), t.begin() + std::min(*n_lut, cap), lut);
+    return st;
+}
+
+// prl_hip_nlm_planes_device through exactly the instantiation `variant` names (numbered as above).  PRL_ERR_BAD_ARG when the
+// variant does not exist for this channel count or the table of (channels, h) does not fit the variant's LDS copy.
+int prl_hip_internal_nlm_variant(int variant, int n_pages, int channels, float h, const uint8_t* d_src, size_t src_page_stride,
+                                 size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                 void* stream)
+{
+    if (variant < 0 || variant >= kNlmVariants) return PRL_ERR_BAD_ARG;
+    return nlm_planes_entry(variant, n_pages, channels, h, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride,
+                            dst_step, stream);
+}
+
+// The two colour conversions of prl::denoise on their own, with the tables and launches of denoise_all_locked.  inverse == 0:
+// n_pages BGR(A) pages at d_bgr -> d_l (one byte per pixel) and d_ab (a, b interleaved), laid out as k_lbgr2lab writes them:
+// page p, row y, column x at index (p * height + y) * width + x.  inverse != 0: the same planes -> BGR(A) pages (alpha 255).
+int prl_hip_internal_lab_convert(int inverse, int n_pages, int channels, uint8_t* d_bgr, size_t page_stride, size_t step, int width,
+                                 int height, uint8_t* d_l, uint8_t* d_ab, void* stream)
+{
+    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    if (channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
+    if (n_pages <= 0 || n_pages > 65535 || height > 65535 || !d_bgr || !d_l || !d_ab || step < (size_t)width * channels)
+        return PRL_ERR_BAD_ARG;
+    int dev;
+    int st = current_device(&dev);
+    if (st != PRL_OK) return st;
+    DeviceCtx* ctx = device_ctx(dev);
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    st = device_acquire(ctx, s);
+    if (st != PRL_OK) return st;
+    DeviceRelease release{ctx, s};
+    LabTables lt{};
+    st = lab_tables(ctx, s, &lt);
+    if (st != PRL_OK) return st;
+    const size_t px = (size_t)width * height;
+    const dim3 grid((width + 255) / 256, height, n_pages);
+    if (inverse)
+        hipLaunchKernelGGL(k_lab2lbgr, grid, dim3(256), 0, s, d_l, d_ab, px, channels, width, height, lt,
+                           page_set_out(d_bgr, page_stride, step));
+    else
+        hipLaunchKernelGGL(k_lbgr2lab, grid, dim3(256), 0, s, page_set(d_bgr, page_stride, step), channels, width, height, lt, d_l,
+                           d_ab, px);
+    PRL_HIP_CHECK(hipGetLastError());
+    return PRL_OK;
+}
+
+}  // extern "C"
+#endif

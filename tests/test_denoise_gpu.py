@@ -3,6 +3,9 @@
 The NLM core is integer arithmetic => bit-exact.  The Lab conversions are restated identically on both
 sides (integer forward, float32 inverse with one rounding per operation) => also compared bit-exactly;
 the documented tolerance of 1 LSB/channel is against a *real* OpenCV build, which is not available.
+
+These tests call the public entries at a few strengths.  tests/test_nlm_gpu.py runs every kernel instantiation by name at the edges
+of the weight table's length, both Lab conversions on all 2^24 triples, and strided / odd-addressed views of the C entries.
 """
 import numpy as np
 import pytest
