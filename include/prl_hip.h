@@ -823,6 +823,102 @@ int prl_hip_warp_crop_batch_device(int n_pages, int channels, const int32_t* qua
 int prl_hip_warp_crop_host(int channels, const int32_t quad[8], double ratio, const uint8_t* src, size_t src_step, int width,
                            int height, uint8_t* dst, size_t dst_step, int border_mode, const double* border_value);
 
+/* ---- pyramid, edge map, resize (cv::pyrDown, cv::Canny, the edge map of prl::documentContour, prl::resize) ------------------ */
+
+/*
+ * The two OpenCV primitives the border detector and prl::resize start from (src/resize.cpp:29-62,
+ * src/border_detection/autoCrop.cpp:67-101), for 8-bit pages in device memory.  Integer arithmetic throughout, so every byte is
+ * held; [upstream] marks what is OpenCV's, as restated in tests/edges_ref.py.  Parity with an installed OpenCV is not pinned
+ * (DESIGN.md §2).  Pages and rows may be strided; a destination has another size than its source and never shares a byte with it.
+ *
+ * cv::pyrDown [upstream], BORDER_REFLECT_101, 1..4 channels, result (W+1)/2 x (H+1)/2.  Per channel
+ *     r(x, j) = s(2x-2, j) + 4 s(2x-1, j) + 6 s(2x, j) + 4 s(2x+1, j) + s(2x+2, j)          columns through R(., W)
+ *     v       = r(x, 2y-2) + 4 r(x, 2y-1) + 6 r(x, 2y) + 4 r(x, 2y+1) + r(x, 2y+2)          rows through R(., H)
+ *     dst     = (v + 128) >> 8
+ * R(p, len) is cv::borderInterpolate: p if 0 <= p < len; 0 if len == 1; else p = -p (p < 0) or 2 len - 2 - p, repeated until
+ * inside (a side of 2 or 3 folds more than once).  `levels` in 1..16 applies the step that many times in one call; the levels
+ * between live in the cached workspace, ordered by the stream alone.
+ *
+ * cv::Canny(src, dst, threshold1, threshold2) [upstream] with apertureSize 3 and L2gradient false, 8UC1 only: a colour page is
+ * PRL_ERR_BAD_CHANNELS (OpenCV takes the channel of largest magnitude per pixel, which is not provided).  threshold1 > threshold2:
+ * swapped.  low = floor(threshold1), high = floor(threshold2), each clamped to [-1, 2041] (every magnitude lies in 0..2040, so no
+ * comparison changes); a NaN is PRL_ERR_BAD_ARG.  With coordinates clamped to the page (BORDER_REPLICATE):
+ *     dx = [p(x+1,y-1) + 2 p(x+1,y) + p(x+1,y+1)] - [p(x-1,y-1) + 2 p(x-1,y) + p(x-1,y+1)]
+ *     dy = [p(x-1,y+1) + 2 p(x,y+1) + p(x+1,y+1)] - [p(x-1,y-1) + 2 p(x,y-1) + p(x+1,y-1)]
+ *     m  = |dx| + |dy|, and m = 0 outside the page
+ * ax = |dx|, ay = |dy| * 2^15, t = ax * 13573.  A pixel is a local maximum iff m > low and
+ *     ay < t:               m > m(x-1,y) and m >= m(x+1,y)
+ *     ay > t + ax * 2^16:   m > m(x,y-1) and m >= m(x,y+1)
+ *     else:                 m > m(x-s,y-1) and m > m(x+s,y+1),  s = -1 if (dx ^ dy) < 0, else +1
+ * Class 2: a local maximum with m > high; class 0: any other local maximum; class 1: the rest (OpenCV's map codes).  The result is
+ * 255 for class 2 and for every class-0 pixel that reaches a class-2 pixel through 8-connected class-0 pixels, 0 elsewhere: a
+ * closure that does not depend on the visiting order, so the parallel fixpoint equals OpenCV's stack walk.  The passes repeat
+ * until no page changes, without a cap; the calls that link wait for the stream (they read the per-page flags back).
+ *
+ * The edge map of prl::documentContour (autoCrop.cpp:67-101), pages of 1, 3 or 4 channels: pyrDown while longSide / 2 >= 256
+ * (longSide from the reduced size each time; 511 gives no level), the channel with the first maximum of cv::meanStdDev's
+ * standard deviations, cv::Canny(25, 50) on it.  The deviations come from the last level's per-channel histograms, on the host in
+ * float64: mean = sum(h v) / N, stddev = sqrt(max(sum(h v^2) / N - mean^2, 0)), both sums exact integers: ONE small read-back
+ * (the bins) per chunk of pages, before the edge map.  Gray pages skip it.  The retries of autoCrop.cpp:118-125 and the contour
+ * search are not provided.
+ *
+ * prl::resize (resize.cpp:29-62).  Pyramid path (scaleX or scaleY not positive): pyrDown while the long side exceeds maxSize;
+ * maxSize < 1 never ends in the reference and is PRL_ERR_BAD_ARG here.  Scale path: cv::resize(INTER_AREA) to cols * scaleX x
+ * rows * scaleY with integer factors >= 1 is an enlargement, which OpenCV [upstream] runs through its bilinear routine with the
+ * coefficient fx = (dx + 1) - (sx + 1) * scaleX, sx = floor(dx * (1.0 / scaleX)) in float64: fx is an integer, its fraction 0, so
+ * dst(dy, dx) = src(min(sy(dy), rows - 1), min(sx(dx), cols - 1)).  The tables come from the product, not from dx / scaleX: at
+ * scaleX = 49 the product 49 * (1.0 / 49) lies below 1 and column 49 copies source column 0.  A result side above 32768 is
+ * PRL_ERR_BAD_ARG.
+ *
+ * Every entry checks in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_CHANNELS;
+ * PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row bytes, levels / factors / thresholds / maxSize as above, sides above
+ * 32768, source and destination sharing a byte).  The *_host entries take one page in host memory and synchronise.
+ */
+
+/* the size after `levels` pyramid levels; host code, no device needed */
+int prl_hip_pyr_down_size(int width, int height, int levels, int* out_w, int* out_h);
+/* d_dst pages hold the last level: prl_hip_pyr_down_size.  Enqueues only. */
+int prl_hip_pyr_down_batch_device(int n_pages, int channels, int levels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                  int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_pyr_down_host(int channels, int levels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst,
+                          size_t dst_step);
+
+/* stage 1 alone: the class of every pixel (0, 1, 2) as bytes.  Enqueues only. */
+int prl_hip_canny_classes_batch_device(int n_pages, int channels, double threshold1, double threshold2, const uint8_t* d_src,
+                                       size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                       size_t dst_page_stride, size_t dst_step, void* stream);
+/* stage 2 alone on a byte class map (2 = edge, 0 = candidate, anything else = no edge) -> 0 / 255.  out_passes (host, n_pages
+ * entries, or NULL) receives the number of linking passes each page took part in; the last of them changed nothing.  Waits for
+ * the stream. */
+int prl_hip_edge_link_batch_device(int n_pages, const uint8_t* d_classes, size_t src_page_stride, size_t src_step, int width, int height,
+                                   uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, int32_t* out_passes, void* stream);
+/* cv::Canny: stage 1 writes two bit planes (strong, candidate), stage 2 links on them, the strong plane leaves as 0 / 255 bytes;
+ * no byte class map is written.  Waits for the stream. */
+int prl_hip_canny_batch_device(int n_pages, int channels, double threshold1, double threshold2, const uint8_t* d_src, size_t src_page_stride,
+                               size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_canny_host(int channels, double threshold1, double threshold2, const uint8_t* src, size_t src_step, int width, int height,
+                       uint8_t* dst, size_t dst_step);
+
+/* the pyramid levels prl::documentContour takes and the size of its edge map; host code, no device needed */
+int prl_hip_document_edges_geometry(int width, int height, int* levels, int* out_w, int* out_h);
+/* d_dst: one 8UC1 map per page of the size prl_hip_document_edges_geometry reports; out_channel (host, n_pages entries): the
+ * channel each page's map was made from.  Reads the bins back once per chunk of pages and waits for the stream. */
+int prl_hip_document_edges_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                        int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, int32_t* out_channel,
+                                        void* stream);
+int prl_hip_document_edges_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step,
+                                int32_t* out_channel);
+
+/* prl::resize, pyramid path: how many levels the reference takes and the size it ends with; host code, no device needed */
+int prl_hip_resize_pyramid_levels(int width, int height, int max_size, int* levels, int* out_w, int* out_h);
+/* prl::resize, scale path: dst is width * scale_x x height * scale_y; factors (1, 1) are a copy.  Enqueues only: nothing is waited
+ * for but the previous call's table copy. */
+int prl_hip_resize_replicate_batch_device(int n_pages, int channels, int scale_x, int scale_y, const uint8_t* d_src, size_t src_page_stride,
+                                          size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                          void* stream);
+int prl_hip_resize_replicate_host(int channels, int scale_x, int scale_y, const uint8_t* src, size_t src_step, int width, int height,
+                                  uint8_t* dst, size_t dst_step);
+
 #ifdef __cplusplus
 }
 #endif

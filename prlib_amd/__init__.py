@@ -15,6 +15,8 @@ from .thinning import thinGuoHall, thinZhangSuen  # noqa: F401
 from .background import backgroundNormalization  # noqa: F401
 from .deskew import deskew, deskew_stats, find_angle as findAngle, find_orientation as findOrientation, houghp, rotate  # noqa: F401
 from .warp import perspective_transform, warp_crop, warp_crop_host, warp_crop_size, warp_perspective  # noqa: F401
+from .edges import (canny, canny_classes, document_edges, document_edges_geometry, edge_link, pyr_down, pyr_down_size, resize,  # noqa: F401
+                    resize_pyramid_levels)
 from .chain import bitwise_not, cvtColorBGR2GRAY, cvtColorGRAY2BGR, process_pages, process_pages_host  # noqa: F401
 from .binarizations import (  # noqa: F401
     FENG, NICK, NIBLACK, SAUVOLA, WOLFJOLION, binarize, binarizeFeng, binarizeNICK, binarizeNiblack,
@@ -25,6 +27,6 @@ from .binarizations import (  # noqa: F401
 __all__ = [
     "binarize", "binarizeSauvola", "binarizeNiblack", "binarizeWolfJolion", "binarizeNICK", "binarizeFeng", "binarizeByLocalVariances", "binarizeByLocalVariancesWithoutFilters",
     "adaptiveThreshold", "binarizeNativeAdaptive", "binarizeAT", "binarizeAGT", "binarizePureAdaptiveGaussian",
-    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
+    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize", "resize_pyramid_levels", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
     "SAUVOLA", "NIBLACK", "WOLFJOLION", "NICK", "FENG",
 ]

@@ -68,6 +68,10 @@ EXPORTED_SYMBOLS = [
     "prl_hip_cooccurrence_batch_device", "prl_hip_mokji_threshold",
     "prl_hip_warp_crop_size", "prl_hip_perspective_transform", "prl_hip_warp_perspective_batch_device",
     "prl_hip_warp_crop_batch_device", "prl_hip_warp_crop_host",
+    "prl_hip_pyr_down_size", "prl_hip_pyr_down_batch_device", "prl_hip_pyr_down_host",
+    "prl_hip_canny_classes_batch_device", "prl_hip_edge_link_batch_device", "prl_hip_canny_batch_device", "prl_hip_canny_host",
+    "prl_hip_document_edges_geometry", "prl_hip_document_edges_batch_device", "prl_hip_document_edges_host",
+    "prl_hip_resize_pyramid_levels", "prl_hip_resize_replicate_batch_device", "prl_hip_resize_replicate_host",
 ]
 
 
@@ -233,6 +237,19 @@ def lib() -> C.CDLL:
         L.prl_hip_warp_perspective_batch_device.argtypes = [i, i, vp, i, vp, sz, sz, i, i, vp, sz, sz, vp, i, vp, vp]
         L.prl_hip_warp_crop_batch_device.argtypes = [i, i, vp, d, vp, sz, sz, i, i, vp, sz, sz, vp, i, vp, vp]
         L.prl_hip_warp_crop_host.argtypes = [i, vp, d, vp, sz, i, i, vp, sz, i, vp]
+        L.prl_hip_pyr_down_size.argtypes = [i, i, i, P(C.c_int), P(C.c_int)]
+        L.prl_hip_pyr_down_batch_device.argtypes = [i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_pyr_down_host.argtypes = [i, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_canny_classes_batch_device.argtypes = [i, i, d, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_edge_link_batch_device.argtypes = [i, vp, sz, sz, i, i, vp, sz, sz, vp, vp]
+        L.prl_hip_canny_batch_device.argtypes = [i, i, d, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_canny_host.argtypes = [i, d, d, vp, sz, i, i, vp, sz]
+        L.prl_hip_document_edges_geometry.argtypes = [i, i, P(C.c_int), P(C.c_int), P(C.c_int)]
+        L.prl_hip_document_edges_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp, vp]
+        L.prl_hip_document_edges_host.argtypes = [i, vp, sz, i, i, vp, sz, vp]
+        L.prl_hip_resize_pyramid_levels.argtypes = [i, i, i, P(C.c_int), P(C.c_int), P(C.c_int)]
+        L.prl_hip_resize_replicate_batch_device.argtypes = [i, i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_resize_replicate_host.argtypes = [i, i, i, vp, sz, i, i, vp, sz]
         _lib = L
     return _lib
 

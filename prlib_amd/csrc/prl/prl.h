@@ -21,6 +21,7 @@
 //   src/cleanBackgroundToWhite.h:40                        prl::cleanBackgroundToWhite
 //   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
 //   src/warp.h:49-73                                       prl::warpCrop
+//   src/resize.h:32                                        prl::resize
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
 // window, binarizeSauvola.cpp:38-47) and side effects: the caller's input Mat is converted to gray
@@ -189,6 +190,14 @@ CV_EXPORTS void warpCrop(const cv::Mat& inputImage, cv::Mat& outputImage, const 
               const cv::Scalar& borderValue = cv::Scalar());
 CV_EXPORTS void warpCrop(cv::Mat& inputImage, cv::Mat& outputImage, const std::vector<cv::Point>& points, double ratio = -1.0,
               int borderMode = 0, const cv::Scalar& borderValue = cv::Scalar());
+
+// src/resize.h:32 (no defaults, as there) - resize.cpp:29-62 (pyr.hip; the arithmetic is stated in prl_hip.h).  scaleX > 0 and
+// scaleY > 0: cv::resize(INTER_AREA) to cols * scaleX x rows * scaleY, an exact replication through OpenCV's float64 index tables.
+// Otherwise dst = src.clone(), then cv::pyrDown while the long side exceeds maxSize.  cv::Exception StsBadArg for maxSize < 1 on
+// that path (the reference loops for ever) and for a result side above 32768; StsAssert for an empty source on the scale path
+// [upstream]; StsUnsupportedFormat for a depth other than CV_8U or more than 4 channels.  On every error dst stays untouched.
+// The output is a new continuous Mat; the input's pixels are never written.
+CV_EXPORTS void resize(const cv::Mat& src, cv::Mat& dst, int scaleX, int scaleY, int maxSize);
 
 // BASELINE config 1 (plumbing, host only): global Otsu, the one global threshold the reference uses
 // (cv::threshold(..., THRESH_BINARY | THRESH_OTSU), src/deskew/deskew.cpp:224).  Not a GPU path.

@@ -501,6 +501,38 @@ void prl::warpCrop(cv::Mat& inputImage, cv::Mat& outputImage, const std::vector<
              points[3].y, ratio, borderMode, borderValue);
 }
 
+void prl::resize(const cv::Mat& src, cv::Mat& dst, int scaleX, int scaleY, int maxSize)
+{
+    const bool by_scale = scaleX > 0 && scaleY > 0;
+    if (!by_scale && maxSize < 1) PRL_FAIL_CV(cv::Error::StsBadArg, "prl::resize: maxSize < 1 (the reference never returns)");
+    if (src.empty()) {
+        if (by_scale) PRL_FAIL_CV(cv::Error::StsAssert, "!ssize.empty()");   // [upstream] cv::resize's own check
+        dst = cv::Mat();                                                     // src.clone(), and no level to take (resize.cpp:49-51)
+        return;
+    }
+    if (src.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::resize: 8-bit images only");
+    if (src.channels() > 4) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::resize: at most 4 channels");
+    int st, levels = 0, ow = src.cols, oh = src.rows;
+    if (by_scale) {
+        if ((long long)src.cols * scaleX > 32768 || (long long)src.rows * scaleY > 32768) raise(PRL_ERR_BAD_ARG);
+        ow = src.cols * scaleX;
+        oh = src.rows * scaleY;
+    } else if ((st = prl_hip_resize_pyramid_levels(src.cols, src.rows, maxSize, &levels, &ow, &oh)) != PRL_OK) {
+        raise(st);
+    }
+    cv::Mat result(oh, ow, src.type());
+    if (by_scale) {
+        st = prl_hip_resize_replicate_host(src.channels(), scaleX, scaleY, src.data, src.step, src.cols, src.rows, result.data, result.step);
+    } else if (levels == 0) {   // dst = src.clone()
+        for (int y = 0; y < src.rows; ++y) std::memcpy(result.ptr(y), src.ptr(y), (size_t)src.cols * src.channels());
+        st = PRL_OK;
+    } else {
+        st = prl_hip_pyr_down_host(src.channels(), levels, src.data, src.step, src.cols, src.rows, result.data, result.step);
+    }
+    if (st != PRL_OK) raise(st);
+    dst = result;
+}
+
 bool prl::deskew(const cv::Mat& inputImage, cv::Mat& outputImage)
 {
     if (inputImage.empty()) PRL_FAIL_CV(cv::Error::StsAssert, "!inputImage.empty()");  // CV_Assert, deskew.cpp:210

@@ -470,6 +470,14 @@ int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& s
 int gmorph_dilate_rect_run(int k, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
                            hipStream_t stream);
 
+// ---- cv::pyrDown (pyr.hip): `levels` >= 1 pyramid levels of n pages of 1..4 channels into `dst` (pages of the last level's size);
+// `work`: n * pyr_work_per_page bytes for the levels between; enqueues only (caller holds ctx->mu) ----------
+size_t pyr_work_per_page(int width, int height, int channels, int levels);
+int pyr_run(int channels, const PageSet& src, int width, int height, int levels, const PageSetOut& dst, int n_pages, uint8_t* work,
+            hipStream_t stream);
+// the destination of an entry whose result is out_width x out_height: its rows, and no byte shared with the source
+int resized_dst_ok(const PageArgs& a, int channels, int out_width, int out_height, bool batch);
+
 // ---- morphology (morph.hip) ------------------------------------------------------------------
 int morph_run(int iterations, const PageSet& src, int n_pages, int width, int height,
               const PageSetOut& dst, hipStream_t stream);
