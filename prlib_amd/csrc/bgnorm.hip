@@ -365,16 +365,15 @@ int prl_hip_bgnorm_batch_device(int n_pages, int channels, const uint8_t* d_src,
 
 int prl_hip_bgnorm_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
 {
-    if (width <= 0 || height <= 0 || !src) return PRL_ERR_EMPTY;
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    if (pages_nonempty(a) != PRL_OK || !src) return PRL_ERR_EMPTY;   // a null image is an empty cv::Mat
     if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
     const int och = channels == 1 ? 1 : 3;
-    if (!dst || src_step < (size_t)width * channels || dst_step < (size_t)width * och) return PRL_ERR_BAD_ARG;
-    const size_t in_row = (size_t)width * channels, out_row = (size_t)width * och;
-    return stage_host_page(src, src_step, in_row, height, dst, dst_step, out_row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return prl_hip_bgnorm_batch_device(1, channels, d_in, in_bytes, in_row, width, height, d_out, out_bytes,
-                                                                  out_row, s);
-                           });
+    const int st = pages_rows_ok(a, channels, och, false);
+    if (st != PRL_OK) return st;
+    return stage_host_pages(a, channels, och, width, height, [&](const PageArgs& p, hipStream_t s) {
+        return prl_hip_bgnorm_batch_device(1, channels, p.src, p.src_page_stride, p.src_step, width, height, p.dst, p.dst_page_stride, p.dst_step, s);
+    });
 }
 
 }  // extern "C"

@@ -1311,16 +1311,12 @@ int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, 
                  const PageSetOut& dst, hipStream_t hs)
 {
     if (plan.warp.size() != sizeof(WarpPage) * (size_t)cnt) return PRL_ERR_BAD_ARG;
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    int st = device_acquire(ctx, hs);
+    WorkScope w;
+    const int st = w.open_on(ctx, hs, 0, plan.warp.size(), 0);
     if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    st = ensure_small(ctx, plan.warp.size());
-    if (st != PRL_OK) return st;
-    ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
-    PRL_HIP_CHECK(hipMemcpyAsync(ctx->small, plan.warp.data(), plan.warp.size(), hipMemcpyHostToDevice, hs));
+    PRL_HIP_CHECK(hipMemcpyAsync(w.small(), plan.warp.data(), plan.warp.size(), hipMemcpyHostToDevice, hs));
     PRL_HIP_CHECK(hipStreamSynchronize(hs));  // pageable source
-    return launch_warp(channels, src, dst, width, height, cnt, plan.max_ow, plan.max_oh, static_cast<const WarpPage*>(ctx->small), hs);
+    return launch_warp(channels, src, dst, width, height, cnt, plan.max_ow, plan.max_oh, w.small<const WarpPage>(), hs);
 }
 
 int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, const PageSetOut& dst,
@@ -1394,24 +1390,19 @@ int prl_hip_rotate_batch_device(int n_pages, int channels, const double* angles,
                                 size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
                                 void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (channels < 1 || channels > 4) return PRL_ERR_BAD_CHANNELS;
-    if (n_pages < 0 || !angles || !d_src || !d_dst || d_src == d_dst || src_step < (size_t)width * channels) return PRL_ERR_BAD_ARG;
-    if (std::max(width, height) > 32767) return PRL_ERR_BAD_ARG;
+    // (the destination's rows are checked per page below, against the page's own result width)
+    if ((st = pages_rows_ok(a, channels, 0, true)) != PRL_OK || !angles || !d_dst || d_src == d_dst) return PRL_ERR_BAD_ARG;
+    if ((st = pages_sides_ok(a, 32767)) != PRL_OK) return st;
     if (n_pages == 0) return PRL_OK;
-    int dev;
-    int st = current_device(&dev);
+    const int chunk = stage_chunk(n_pages, 0, 0, 32768);
+    WorkScope w;
+    st = w.open(stream, 0, sizeof(WarpPage) * (size_t)chunk, 0);
     if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    const int chunk = std::min(n_pages, 32768);
-    st = ensure_small(ctx, sizeof(WarpPage) * (size_t)chunk);
-    if (st != PRL_OK) return st;
-    ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
+    const hipStream_t hs = w.stream;
     std::vector<WarpPage> wp((size_t)chunk);
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
@@ -1422,11 +1413,9 @@ int prl_hip_rotate_batch_device(int n_pages, int channels, const double* angles,
             max_oh = std::max(max_oh, wp[(size_t)i].oh);
             if (dst_step < (size_t)wp[(size_t)i].ow * channels) return PRL_ERR_BAD_ARG;
         }
-        PRL_HIP_CHECK(hipMemcpyAsync(ctx->small, wp.data(), sizeof(WarpPage) * (size_t)cnt, hipMemcpyHostToDevice, hs));
+        PRL_HIP_CHECK(hipMemcpyAsync(w.small(), wp.data(), sizeof(WarpPage) * (size_t)cnt, hipMemcpyHostToDevice, hs));
         PRL_HIP_CHECK(hipStreamSynchronize(hs));  // `wp` is pageable host memory reused by the next chunk
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
-        st = launch_warp(channels, s, d, width, height, cnt, max_ow, max_oh, static_cast<const WarpPage*>(ctx->small), hs);
+        st = launch_warp(channels, src_pages(a, first), dst_pages(a, first), width, height, cnt, max_ow, max_oh, w.small<const WarpPage>(), hs);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;

@@ -356,40 +356,36 @@ __global__ void __launch_bounds__(256) k_lv_final(LvParams p, const uint8_t* __r
 
 using namespace prl_hip;
 
+static int lv_chunk(int n_pages) { return stage_chunk(n_pages, 0, 0, 16384); }   // pages per launch sequence (no byte budget)
+
 // The launch sequence of the C entry and of the test-hooks entry below.  out_G / out_N / out_consts (device memory; all null from
-// the product entry, all set and n_pages <= 16384 from the hooks entry): after the last kernel, on the same stream and before
-// the workspace is released, the dense n x height x width planes of G and N and the eight floats per page of LvConsts.
-static int lv_run(int n_pages, int with_filters, double coeff, int min_result_variance, double gamma, const uint8_t* d_src,
-                  size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
-                  size_t dst_step, uint8_t* out_G, uint8_t* out_N, float* out_consts, void* stream)
+// the product entry, all set and the pages within one chunk from the hooks entry): after the last kernel, on the same stream and
+// before the workspace is released, the dense n x height x width planes of G and N and the eight floats per page of LvConsts.
+static int lv_run(const PageArgs& a, int with_filters, double coeff, int min_result_variance, double gamma, uint8_t* out_G,
+                  uint8_t* out_N, float* out_consts, void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;  // binarizeByLocalVariances.cpp:16-19, :151-154
-    if (n_pages < 0 || !d_src || !d_dst || src_step < (size_t)width * 3 || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
+    const int n_pages = a.n_pages, width = a.width, height = a.height;
+    int st = pages_nonempty(a);  // binarizeByLocalVariances.cpp:16-19, :151-154
+    if (st != PRL_OK) return st;
+    if ((st = pages_rows_ok(a, 3, 1, true)) != PRL_OK) return st;
     if ((height + MY - 1) / MY > 65535) return PRL_ERR_BAD_ARG;
     if (n_pages == 0) return PRL_OK;
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    std::lock_guard<std::mutex> lk(ctx->mu);
     const size_t plane = r256((size_t)width * height);
-    const int chunk = std::min(n_pages, 16384);
+    const int chunk = lv_chunk(n_pages);
     const size_t stats_bytes = r256((size_t)chunk * (sizeof(LvStats) + sizeof(LvConsts)));
-    st = ensure_scratch(ctx, stats_bytes + (with_filters ? 2 * plane * (size_t)chunk : 0));
+    WorkScope w;
+    st = w.open(stream, stats_bytes + (with_filters ? 2 * plane * (size_t)chunk : 0), 0, 0);
     if (st != PRL_OK) return st;
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    LvStats* d_stats = static_cast<LvStats*>(ctx->scratch);
+    const hipStream_t hs = w.stream;
+    LvStats* d_stats = w.scratch<LvStats>();
     LvConsts* d_consts = reinterpret_cast<LvConsts*>(d_stats + chunk);
-    uint8_t* G = static_cast<uint8_t*>(ctx->scratch) + stats_bytes;
+    uint8_t* G = w.scratch() + stats_bytes;
     uint8_t* NR = G + plane * (size_t)chunk;
     LvParams p{width, height, with_filters ? 1 : 0, min_result_variance, coeff, gamma};
     for (int first = 0; first < n_pages; first += chunk) {
         const int cnt = std::min(chunk, n_pages - first);
-        const PageSet s = pages_from(page_set(d_src, src_page_stride, src_step), first);
-        const PageSetOut d = pages_from(page_set_out(d_dst, dst_page_stride, dst_step), first);
+        const PageSet s = src_pages(a, first);
+        const PageSetOut d = dst_pages(a, first);
         const dim3 grid((unsigned)((width + FX - 1) / FX), (unsigned)((height + FY - 1) / FY), (unsigned)cnt);    // k_lv_final
         const dim3 mgrid((unsigned)((width + MX - 1) / MX), (unsigned)((height + MY - 1) / MY), (unsigned)cnt);   // variance passes
         hipLaunchKernelGGL(k_lv_init, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, hs, d_stats, cnt);
@@ -417,35 +413,35 @@ int prl_hip_binarize_lv_batch_device(int n_pages, int with_filters, double coeff
                                      const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
                                      uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    return lv_run(n_pages, with_filters, coeff, min_result_variance, gamma, d_src, src_page_stride, src_step, width, height, d_dst,
-                  dst_page_stride, dst_step, nullptr, nullptr, nullptr, stream);
+    return lv_run(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, with_filters, coeff,
+                  min_result_variance, gamma, nullptr, nullptr, nullptr, stream);
 }
 
 #ifdef PRL_TEST_HOOKS
 // libprlib_hip_testhooks.so only: the filtered variant through the product entry's own launch sequence, and what pass 2 left in
 // scratch.  d_G, d_N: n_pages x height x width bytes; d_consts: n_pages x 8 floats (thr[3], ga, gb, lmean, two of padding); all
-// three in device memory.  At most 16384 pages (one chunk: the scratch of a later chunk overwrites the one before it).
+// three in device memory.  The pages of one chunk at most (16384, or what PRL_HIP_STAGE_CHUNK leaves of it: the scratch of a
+// later chunk overwrites the one before it).
 int prl_hip_internal_lv_maps(int n_pages, double coeff, int min_result_variance, double gamma, const uint8_t* d_src,
                              size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
                              size_t dst_step, uint8_t* d_G, uint8_t* d_N, float* d_consts, void* stream)
 {
-    if (n_pages > 16384 || !d_G || !d_N || !d_consts) return PRL_ERR_BAD_ARG;
-    return lv_run(n_pages, 1, coeff, min_result_variance, gamma, d_src, src_page_stride, src_step, width, height, d_dst,
-                  dst_page_stride, dst_step, d_G, d_N, d_consts, stream);
+    if (n_pages > lv_chunk(n_pages) || !d_G || !d_N || !d_consts) return PRL_ERR_BAD_ARG;
+    return lv_run(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, 1, coeff,
+                  min_result_variance, gamma, d_G, d_N, d_consts, stream);
 }
 #endif
 
 int prl_hip_binarize_lv_host(int with_filters, double coeff, int min_result_variance, double gamma, const uint8_t* src,
                              size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
 {
-    if (width <= 0 || height <= 0 || !src) return PRL_ERR_EMPTY;
-    if (!dst || src_step < (size_t)width * 3 || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    const size_t in_row = (size_t)width * 3, out_row = (size_t)width;
-    return stage_host_page(src, src_step, in_row, height, dst, dst_step, out_row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return prl_hip_binarize_lv_batch_device(1, with_filters, coeff, min_result_variance, gamma, d_in, in_bytes,
-                                                                       in_row, width, height, d_out, out_bytes, out_row, s);
-                           });
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    if (pages_nonempty(a) != PRL_OK || !src) return PRL_ERR_EMPTY;   // a null image is an empty cv::Mat
+    const int st = pages_rows_ok(a, 3, 1, false);
+    if (st != PRL_OK) return st;
+    return stage_host_pages(a, 3, 1, width, height, [&](const PageArgs& page, hipStream_t s) {
+        return lv_run(page, with_filters, coeff, min_result_variance, gamma, nullptr, nullptr, nullptr, s);
+    });
 }
 
 }  // extern "C"

@@ -854,11 +854,15 @@ namespace prl_hip {
 // kernels) away from the angle search of the next pass and only the middle one beside it (glue.hip).
 size_t denoise_plane_bytes(int width, int height) { return 6 * (size_t)width * height; }
 
+// What every NL-means call asks of `small`: the two weight tables, which stay valid from call to call (kKeepNlmTables), and
+// the cube-root table behind them.
+constexpr size_t kNlmSmallBytes = 2 * kLutSlot + 64 * 1024;
+
+// The Lab conversions' constants; the cube-root table goes to `small` behind the two weight-table slots.  The caller has a
+// WorkScope open that asked for kNlmSmallBytes of `small` (nothing is sized here); the status is that of the copy alone.
 static int lab_tables(DeviceCtx* ctx, hipStream_t s, LabTables* lt)
 {
     const size_t cbrt_off = 2 * kLutSlot;
-    int st = ensure_small(ctx, cbrt_off + 64 * 1024);
-    if (st != PRL_OK) return st;
     const HostLab& hl = host_lab();
     auto* d_cbrt = reinterpret_cast<unsigned short*>(static_cast<uint8_t*>(ctx->small) + cbrt_off);
     PRL_HIP_CHECK(hipMemcpyAsync(d_cbrt, hl.cbrt_tab.data(), hl.cbrt_tab.size() * sizeof(unsigned short), hipMemcpyHostToDevice, s));
@@ -868,13 +872,11 @@ static int lab_tables(DeviceCtx* ctx, hipStream_t s, LabTables* lt)
     return PRL_OK;
 }
 
+// (the *_locked parts run under their caller's WorkScope, as lab_tables does)
 static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const PageSet& ps, int width, int height, uint8_t* planes, hipStream_t s)
 {
-    int st = device_acquire(ctx, s);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, s};
     LabTables lt{};
-    st = lab_tables(ctx, s, &lt);
+    int st = lab_tables(ctx, s, &lt);
     if (st != PRL_OK) return st;
     const size_t px = (size_t)width * height;
     uint8_t* L = planes;
@@ -887,9 +889,6 @@ static int convert_in_locked(DeviceCtx* ctx, int cnt, int channels, const PageSe
 
 static int nlm_locked(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int width, int height, hipStream_t s)
 {
-    int st = device_acquire(ctx, s);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, s};
     const size_t px = (size_t)width * height;
     uint8_t* L = planes;
     uint8_t* AB = L + px * (size_t)cnt;
@@ -897,7 +896,7 @@ static int nlm_locked(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, 
     uint8_t* AB2 = L2 + px * (size_t)cnt;
     const PageSet sl = page_set(L, px, (size_t)width), sab = page_set(AB, 2 * px, 2 * (size_t)width);
     const PageSetOut dl = page_set_out(L2, px, (size_t)width), dab = page_set_out(AB2, 2 * px, 2 * (size_t)width);
-    st = nlm_planes_locked(ctx, 0, cnt, 1, strength, sl, width, height, dl, s);
+    const int st = nlm_planes_locked(ctx, 0, cnt, 1, strength, sl, width, height, dl, s);
     if (st != PRL_OK) return st;
     return nlm_planes_locked(ctx, 1, cnt, 2, 3.0f, sab, width, height, dab, s);  // hForColorComponents = 3
 }
@@ -905,11 +904,8 @@ static int nlm_locked(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, 
 static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, const PageSetOut& pd,
                               hipStream_t s)
 {
-    int st = device_acquire(ctx, s);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, s};
     LabTables lt{};
-    st = lab_tables(ctx, s, &lt);
+    int st = lab_tables(ctx, s, &lt);
     if (st != PRL_OK) return st;
     const size_t px = (size_t)width * height;
     const uint8_t* L2 = planes + 3 * px * (size_t)cnt;
@@ -920,59 +916,83 @@ static int convert_out_locked(DeviceCtx* ctx, int cnt, int channels, const uint8
     return PRL_OK;
 }
 
-int denoise_convert_in(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, uint8_t* planes, hipStream_t s)
-{
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return convert_in_locked(ctx, cnt, channels, src, width, height, planes, s);
-}
-int denoise_nlm(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int width, int height, hipStream_t s)
-{
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return nlm_locked(ctx, cnt, strength, planes, width, height, s);
-}
-int denoise_convert_out(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, const PageSetOut& dst,
-                        hipStream_t s)
-{
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    return convert_out_locked(ctx, cnt, channels, planes, width, height, dst, s);
-}
-// the whole stage on pages [0, cnt) with the planes in the shared scratch area: one lock over all three parts
-int denoise_all_locked(DeviceCtx* ctx, int cnt, int channels, float strength, const PageSet& src, int width, int height,
-                       const PageSetOut& dst, uint8_t* planes, hipStream_t s)
+// the whole stage on pages [0, cnt) with the planes in the shared scratch area
+static int denoise_all_locked(DeviceCtx* ctx, int cnt, int channels, float strength, const PageSet& src, int width, int height,
+                              const PageSetOut& dst, uint8_t* planes, hipStream_t s)
 {
     int st = convert_in_locked(ctx, cnt, channels, src, width, height, planes, s);
     if (st == PRL_OK) st = nlm_locked(ctx, cnt, strength, planes, width, height, s);
     if (st == PRL_OK) st = convert_out_locked(ctx, cnt, channels, planes, width, height, dst, s);
     return st;
 }
+
+// The chain's three calls: each one scope on the context the chain holds.
+int denoise_convert_in(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, uint8_t* planes, hipStream_t s)
+{
+    WorkScope w;
+    const int st = w.open_on(ctx, s, 0, kNlmSmallBytes, 0, kKeepNlmTables);
+    return st != PRL_OK ? st : convert_in_locked(ctx, cnt, channels, src, width, height, planes, s);
+}
+int denoise_nlm(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int width, int height, hipStream_t s)
+{
+    WorkScope w;
+    const int st = w.open_on(ctx, s, 0, kNlmSmallBytes, 0, kKeepNlmTables);
+    return st != PRL_OK ? st : nlm_locked(ctx, cnt, strength, planes, width, height, s);
+}
+int denoise_convert_out(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, const PageSetOut& dst,
+                        hipStream_t s)
+{
+    WorkScope w;
+    const int st = w.open_on(ctx, s, 0, kNlmSmallBytes, 0, kKeepNlmTables);
+    return st != PRL_OK ? st : convert_out_locked(ctx, cnt, channels, planes, width, height, dst, s);
+}
 }  // namespace prl_hip
 
 using namespace prl_hip;
 
 // prl_hip_nlm_planes_device; variant >= 0 (test-hooks entry): that instantiation instead of the one nlm_variant picks
-static int nlm_planes_entry(int variant, int n_pages, int channels, float h, const uint8_t* d_src, size_t src_page_stride,
-                            size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
-                            void* stream)
+static int nlm_planes_entry(int variant, const PageArgs& a, int channels, float h, void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
     if (channels < 1 || channels > 3) return PRL_ERR_BAD_CHANNELS;
-    if (n_pages < 0 || !d_src || !d_dst || d_src == d_dst) return PRL_ERR_BAD_ARG;
-    if (src_step < (size_t)width * channels || dst_step < (size_t)width * channels) return PRL_ERR_BAD_ARG;
-    if (n_pages == 0) return PRL_OK;
-    int dev;
-    int st = current_device(&dev);
+    if ((st = pages_rows_ok(a, channels, channels, true)) != PRL_OK || a.src == a.dst) return PRL_ERR_BAD_ARG;
+    if (a.n_pages == 0) return PRL_OK;
+    WorkScope w;
+    st = w.open(stream, 0, kNlmSmallBytes, 0, kKeepNlmTables);
     if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    st = ensure_small(ctx, 2 * kLutSlot + 64 * 1024);
+    return nlm_planes_locked(w.ctx, 0, a.n_pages, channels, h, src_pages(a, 0), a.width, a.height, dst_pages(a, 0), w.stream, variant);
+}
+
+static int denoise_checks(const PageArgs& a, int channels, bool batch)
+{
+    const int st = pages_nonempty(a);
     if (st != PRL_OK) return st;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    st = device_acquire(ctx, s);
+    // "Type of input image should be CV_8UC3 or CV_8UC4!" [upstream fastNlMeansDenoisingColored]
+    if (channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
+    return pages_rows_ok(a, channels, channels, batch);
+}
+
+static int denoise_batch(const PageArgs& a, int channels, float strength, void* stream)
+{
+    int st = denoise_checks(a, channels, true);
     if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, s};
-    const PageSet ps = page_set(d_src, src_page_stride, src_step);
-    const PageSetOut pd = page_set_out(d_dst, dst_page_stride, dst_step);
-    return nlm_planes_locked(ctx, 0, n_pages, channels, h, ps, width, height, pd, s, variant);
+    if (a.n_pages == 0) return PRL_OK;
+    if (a.height > 65535) return PRL_ERR_BAD_ARG;  // the colour conversions use one grid row per image row
+    // planes: L, ab, L', ab'  (1 + 2 + 1 + 2 bytes per pixel), processed in page chunks of bounded size: at most 2 GiB of
+    // them and grid.z of the per-page kernels, one page at least (arithmetically min(max(1, min(n, 2 GiB / 6 px)), 65535), the
+    // rule this entry used to spell out)
+    const size_t px = (size_t)a.width * a.height;
+    const int chunk = stage_chunk(a.n_pages, 6 * px, (size_t)2 << 30, 65535);
+    WorkScope w;
+    st = w.open(stream, 6 * px * (size_t)chunk, kNlmSmallBytes, 0, kKeepNlmTables);
+    if (st != PRL_OK) return st;
+    for (int first = 0; first < a.n_pages; first += chunk) {
+        st = denoise_all_locked(w.ctx, std::min(chunk, a.n_pages - first), channels, strength, src_pages(a, first), a.width, a.height,
+                                dst_pages(a, first), w.scratch(), w.stream);
+        if (st != PRL_OK) return st;
+    }
+    return PRL_OK;
 }
 
 extern "C" {
@@ -981,57 +1001,26 @@ int prl_hip_nlm_planes_device(int n_pages, int channels, float h, const uint8_t*
                               size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
                               size_t dst_step, void* stream)
 {
-    return nlm_planes_entry(-1, n_pages, channels, h, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride,
-                            dst_step, stream);
+    return nlm_planes_entry(-1, PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step},
+                            channels, h, stream);
 }
 
 int prl_hip_denoise_batch_device(int n_pages, int channels, float strength, const uint8_t* d_src,
                                  size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
                                  size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    // "Type of input image should be CV_8UC3 or CV_8UC4!" [upstream fastNlMeansDenoisingColored]
-    if (channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
-    if (n_pages < 0 || !d_src || !d_dst) return PRL_ERR_BAD_ARG;
-    if (src_step < (size_t)width * channels || dst_step < (size_t)width * channels) return PRL_ERR_BAD_ARG;
-    if (n_pages == 0) return PRL_OK;
-    if (height > 65535) return PRL_ERR_BAD_ARG;  // the colour conversions use one grid row per image row
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    // planes: L, ab, L', ab'  (1 + 2 + 1 + 2 bytes per pixel), processed in page chunks of bounded size
-    const size_t px = (size_t)width * height;
-    const size_t budget = (size_t)2 << 30;
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_pages, budget / (6 * px)));
-    chunk = std::min(chunk, 65535);  // grid.z of the per-page kernels
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    st = ensure_scratch(ctx, 6 * px * (size_t)chunk);
-    if (st != PRL_OK) return st;
-    auto* base = static_cast<uint8_t*>(ctx->scratch);
-    const PageSet src = page_set(d_src, src_page_stride, src_step);
-    const PageSetOut dst = page_set_out(d_dst, dst_page_stride, dst_step);
-    for (int first = 0; first < n_pages; first += chunk) {
-        const int cnt = std::min(chunk, n_pages - first);
-        st = denoise_all_locked(ctx, cnt, channels, strength, pages_from(src, first), width, height, pages_from(dst, first), base,
-                                static_cast<hipStream_t>(stream));
-        if (st != PRL_OK) return st;
-    }
-    return PRL_OK;
+    return denoise_batch(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
+                         strength, stream);
 }
 
 int prl_hip_denoise_host(int channels, float strength, const uint8_t* src, size_t src_step, int width, int height,
                          uint8_t* dst, size_t dst_step)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
-    if (!src || !dst || src_step < (size_t)width * channels || dst_step < (size_t)width * channels) return PRL_ERR_BAD_ARG;
-    const size_t row = (size_t)width * channels;
-    return stage_host_page(src, src_step, row, height, dst, dst_step, row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return prl_hip_denoise_batch_device(1, channels, strength, d_in, in_bytes, row, width, height, d_out,
-                                                                   out_bytes, row, s);
-                           });
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const int st = denoise_checks(a, channels, false);
+    if (st != PRL_OK) return st;
+    return stage_host_pages(a, channels, channels, width, height,
+                            [&](const PageArgs& page, hipStream_t s) { return denoise_batch(page, channels, strength, s); });
 }
 
 }  // extern "C"
@@ -1062,8 +1051,8 @@ int prl_hip_internal_nlm_variant(int variant, int n_pages, int channels, float h
                                  void* stream)
 {
     if (variant < 0 || variant >= kNlmVariants) return PRL_ERR_BAD_ARG;
-    return nlm_planes_entry(variant, n_pages, channels, h, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride,
-                            dst_step, stream);
+    return nlm_planes_entry(variant, PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step},
+                            channels, h, stream);
 }
 
 // The two colour conversions of prl::denoise on their own, with the tables and launches of denoise_all_locked.  inverse == 0:
@@ -1076,17 +1065,12 @@ int prl_hip_internal_lab_convert(int inverse, int n_pages, int channels, uint8_t
     if (channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
     if (n_pages <= 0 || n_pages > 65535 || height > 65535 || !d_bgr || !d_l || !d_ab || step < (size_t)width * channels)
         return PRL_ERR_BAD_ARG;
-    int dev;
-    int st = current_device(&dev);
+    WorkScope w;
+    int st = w.open(stream, 0, kNlmSmallBytes, 0, kKeepNlmTables);
     if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    st = device_acquire(ctx, s);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, s};
+    const hipStream_t s = w.stream;
     LabTables lt{};
-    st = lab_tables(ctx, s, &lt);
+    st = lab_tables(w.ctx, s, &lt);
     if (st != PRL_OK) return st;
     const size_t px = (size_t)width * height;
     const dim3 grid((width + 255) / 256, height, n_pages);

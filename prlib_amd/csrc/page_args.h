@@ -1,7 +1,10 @@
-// page_args.h — the page arguments every stage entry shares (median, adaptive, gmorph, lines, tone, mokji, warp, bgnorm), the
-// checks made on them and the rule that cuts a batch into chunks of pages.  Plain C++17: no HIP header, no environment, no
-// I/O - tests/cpp/test_page_args.cpp drives it on the CPU.  An entry lists the check pieces in its own documented order, with
-// its stage-specific checks in between; every piece returns a PRL_* status and touches no device.
+// page_args.h — the page arguments every stage entry shares (median, adaptive, gmorph, lines, tone, mokji, warp, bgnorm, pyr,
+// canny, thinning, the local-variance binarizers, NL-means and denoise, the mask morphology, rotate, and the single-page *_host
+// entries of all of them and of the binarizers), the checks made on them and the rule that cuts a batch into chunks of pages.
+// Plain C++17: no HIP header, no environment, no I/O - tests/cpp/test_page_args.cpp drives it on the CPU.  An entry lists the
+// check pieces in its own documented order, with its stage-specific checks in between (the older entries refuse source ==
+// destination by pointer, or not at all, where the newer ones use pages_overlap_ok); every piece returns a PRL_* status and
+// touches no device.
 #pragma once
 
 #include <algorithm>

@@ -1270,13 +1270,12 @@ int prl_hip_binarize_host(const prl_binarize_params* p, const uint8_t* src, size
     if (!src || !dst || src_step < (size_t)width || dst_step < (size_t)g.out_w) return PRL_ERR_BAD_ARG;
     if (padded_out && padded_step < (size_t)g.padded_w) return PRL_ERR_BAD_ARG;
     // rows packed tightly on the device (the kernels take any step >= width)
-    const size_t in_pitch = (size_t)width, out_pitch = (size_t)g.out_w;
-    st = stage_host_page(src, src_step, in_pitch, height, dst, dst_step, out_pitch, g.out_h,
-                         [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                             const int r = prl_hip_binarize_batch_device(p, 1, d_in, in_bytes, in_pitch, width, height, d_out,
-                                                                         out_bytes, out_pitch, s);
-                             return r != PRL_OK ? r : prl_hip_finish(s);  // (deferred-completion mode: the page is final before it is fetched)
-                         });
+    st = stage_host_pages(PageArgs{1, src, 0, src_step, width, height, dst, 0, dst_step}, 1, 1, g.out_w, g.out_h,
+                          [&](const PageArgs& page, hipStream_t s) {
+                              const int r = prl_hip_binarize_batch_device(p, 1, page.src, page.src_page_stride, page.src_step, width, height,
+                                                                          page.dst, page.dst_page_stride, page.dst_step, s);
+                              return r != PRL_OK ? r : prl_hip_finish(s);  // (deferred-completion mode: the page is final before it is fetched)
+                          });
     if (st != PRL_OK) return st;
     if (padded_out) {
         // cv::copyMakeBorder(in, in, h, h, h, h, BORDER_REPLICATE) side effect on the caller's Mat
@@ -1297,45 +1296,34 @@ int prl_hip_morph_batch_device(int morph_iterations, int n_pages, const uint8_t*
                                size_t src_page_stride, size_t src_step, int width, int height,
                                uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (n_pages < 0 || !d_src || !d_dst || d_src == d_dst) return PRL_ERR_BAD_ARG;
-    if (src_step < (size_t)width || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    if (n_pages == 0) return PRL_OK;
-    if (n_pages > kMaxPagesPerLaunch) {  // the page index sits in a grid dimension limited to 65535
-        for (int first = 0; first < n_pages; first += kMaxPagesPerLaunch) {
-            const int st2 = prl_hip_morph_batch_device(morph_iterations, std::min(kMaxPagesPerLaunch, n_pages - first),
-                                                       d_src + (size_t)first * src_page_stride, src_page_stride, src_step, width,
-                                                       height, d_dst + (size_t)first * dst_page_stride, dst_page_stride, dst_step,
-                                                       stream);
-            if (st2 != PRL_OK) return st2;
-        }
-        return PRL_OK;
-    }
-    int dev;
-    int st = current_device(&dev);
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    int st = pages_nonempty(a);
     if (st != PRL_OK) return st;
+    if ((st = pages_rows_ok(a, 1, 1, true)) != PRL_OK || d_src == d_dst) return PRL_ERR_BAD_ARG;
+    if (n_pages == 0) return PRL_OK;
+    int dev;
+    if ((st = current_device(&dev)) != PRL_OK) return st;
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
     if (morph_iterations == 0) {
         for (int i = 0; i < n_pages; ++i)
-            PRL_HIP_CHECK(hipMemcpy2DAsync(d_dst + (size_t)i * dst_page_stride, dst_step,
-                                           d_src + (size_t)i * src_page_stride, src_step, (size_t)width,
-                                           (size_t)height, hipMemcpyDeviceToDevice,
-                                           static_cast<hipStream_t>(stream)));
+            PRL_HIP_CHECK(hipMemcpy2DAsync(d_dst + (size_t)i * dst_page_stride, dst_step, d_src + (size_t)i * src_page_stride, src_step,
+                                           (size_t)width, (size_t)height, hipMemcpyDeviceToDevice, hs));
         return PRL_OK;
     }
-    const PageSet s = page_set(d_src, src_page_stride, src_step);
-    const PageSetOut d = page_set_out(d_dst, dst_page_stride, dst_step);
-    if (std::abs(morph_iterations) <= kMorphMaxFusedRadius)
-        return morph_run(morph_iterations, s, n_pages, width, height, d, static_cast<hipStream_t>(stream));
-    DeviceCtx* ctx = device_ctx(dev);
-    std::lock_guard<std::mutex> lk(ctx->mu);
+    // the page index sits in a grid dimension limited to 65535; only a radius above the fused kernels' takes workspace: a `tmp`
+    // plane per page of the chunk
+    const int chunk = stage_chunk(n_pages, 0, 0, kMaxPagesPerLaunch);
+    const bool large = std::abs(morph_iterations) > kMorphMaxFusedRadius;
     const size_t tstep = ((size_t)width + 63) / 64 * 64;
-    st = ensure_scratch(ctx, tstep * (size_t)height * (size_t)n_pages);
-    if (st != PRL_OK) return st;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    st = device_acquire(ctx, hs);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, hs};
-    return morph_large_run(morph_iterations, s, n_pages, width, height, d, static_cast<uint8_t*>(ctx->scratch), tstep, hs);
+    WorkScope w;
+    if (large && (st = w.open_on(device_ctx(dev), hs, tstep * (size_t)height * (size_t)chunk, 0, 0)) != PRL_OK) return st;
+    for (int first = 0; first < n_pages; first += chunk) {
+        const int cnt = std::min(chunk, n_pages - first);
+        st = large ? morph_large_run(morph_iterations, src_pages(a, first), cnt, width, height, dst_pages(a, first), w.scratch(), tstep, hs)
+                   : morph_run(morph_iterations, src_pages(a, first), cnt, width, height, dst_pages(a, first), hs);
+        if (st != PRL_OK) return st;
+    }
+    return PRL_OK;
 }
 
 }  // extern "C"

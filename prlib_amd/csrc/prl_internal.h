@@ -61,7 +61,7 @@ struct DeviceCtx {
     int cu_count = 0;
     hipEvent_t prof_start = nullptr, prof_stop = nullptr;  // prl_hip_set_profiling
     bool prof_valid = false;
-    hipEvent_t last_use = nullptr;  // last use of scratch / small / pinned: device_acquire waits on it, DeviceRelease records it
+    hipEvent_t last_use = nullptr;  // last use of scratch / small / pinned: a WorkScope waits on it when it opens and records it when it ends
     hipEvent_t stage_use = nullptr; // same for the staging area (`stage`): recorded by its last user (guarded by stage_mu)
     hipEvent_t pinned_use = nullptr; // the last asynchronous copy OUT of `pinned` (warp.hip's page records): the host waits for it before it overwrites the block (guarded by mu)
     // The angle search of prl::deskew has its own workspace, lock and stream: in the chain it runs for the next pass
@@ -158,37 +158,57 @@ hipError_t free_host_buffer(void** buf, size_t* have);
 int ensure_scratch(DeviceCtx* ctx, size_t bytes);
 int ensure_small(DeviceCtx* ctx, size_t bytes);   // at least 1 MiB
 int ensure_pinned(DeviceCtx* ctx, size_t bytes);  // at least 64 KiB
-// The shared device workspace (scratch, small, pinned) serves every stream of the device: under `mu`, a user makes its stream
-// wait for the previous user's work (device_acquire) before the first write; DeviceRelease records its own work as the new
-// last use on every exit of the scope, error exits included (before `mu` is released: declare it after the lock).
+// The shared device workspace (scratch, small, pinned) serves every stream of the device, one call at a time: a WorkScope,
+// which alone takes `mu`, makes its stream wait for the previous user's work (device_acquire) before the first write and records
+// its own work as the new last use when it ends.
 int device_acquire(DeviceCtx* ctx, hipStream_t stream);
-struct DeviceRelease {
-    DeviceCtx* c; hipStream_t s;
-    ~DeviceRelease() { (void)hipEventRecord(c->last_use, s); }
-};
-// One call on the shared workspace, from the checks' end to the return: open() takes the current device, its context and `mu`,
-// grows the blocks the call asks for (0 bytes: not needed), drops NL-means' cached tables whenever `small` is asked for (its
-// head is about to be overwritten) and makes the stream wait for the previous user.  On every exit after a successful open()
-// the call's work is recorded as the new last use before `mu` is released, as DeviceRelease does.
+// One call on the shared workspace, from the checks' end to the return, in two steps.  lock() takes the current device (lock_on():
+// the context its caller already holds) and `mu`; grow() sizes the blocks the call asks for (0 bytes: not needed), drops NL-means'
+// cached tables whenever `small` is asked for (its head is about to be overwritten; NL-means itself passes kKeepNlmTables) and
+// makes the stream wait for the previous user.  open() / open_on() are the two in sequence; an entry that may still refuse its arguments
+// after the device check, before anything is allocated, calls them apart (thin.hip).  On every exit after a successful grow(),
+// error exits included, the call's work is recorded as the new last use before `mu` is released.
+// Not on it, each with a workspace and lock of its own: deskew.hip's host_roundtrip (its own buffers, a result size per page),
+// the find_angle / houghp entries and everything else under `ppht_mu`.
+enum class NlmTables { kDrop, kKeep };   // (a type of its own: no size can be passed in its place)
+constexpr NlmTables kKeepNlmTables = NlmTables::kKeep;
 class WorkScope {
 public:
     DeviceCtx* ctx = nullptr;
     hipStream_t stream = nullptr;
-    int open(void* stream_arg, size_t scratch_bytes, size_t small_bytes, size_t pinned_bytes)
+    void lock_on(DeviceCtx* c, hipStream_t s)
+    {
+        ctx = c;
+        stream = s;
+        lk_ = std::unique_lock<std::mutex>(ctx->mu);
+    }
+    int lock(void* stream_arg)
     {
         int dev;
-        int st = current_device(&dev);
-        if (st != PRL_OK) return st;
-        ctx = device_ctx(dev);
-        stream = static_cast<hipStream_t>(stream_arg);
-        lk_ = std::unique_lock<std::mutex>(ctx->mu);
+        const int st = current_device(&dev);
+        if (st == PRL_OK) lock_on(device_ctx(dev), static_cast<hipStream_t>(stream_arg));
+        return st;
+    }
+    int grow(size_t scratch_bytes, size_t small_bytes, size_t pinned_bytes, NlmTables tables = NlmTables::kDrop)
+    {
+        int st;
         if (scratch_bytes && (st = ensure_scratch(ctx, scratch_bytes)) != PRL_OK) return st;
         if (small_bytes && (st = ensure_small(ctx, small_bytes)) != PRL_OK) return st;
         if (pinned_bytes && (st = ensure_pinned(ctx, pinned_bytes)) != PRL_OK) return st;
-        if (small_bytes) ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
+        if (small_bytes && tables == NlmTables::kDrop) ctx->lut_small[0] = ctx->lut_small[1] = nullptr;
         st = device_acquire(ctx, stream);
         acquired_ = st == PRL_OK;
         return st;
+    }
+    int open(void* stream_arg, size_t scratch_bytes, size_t small_bytes, size_t pinned_bytes, NlmTables tables = NlmTables::kDrop)
+    {
+        const int st = lock(stream_arg);
+        return st != PRL_OK ? st : grow(scratch_bytes, small_bytes, pinned_bytes, tables);
+    }
+    int open_on(DeviceCtx* c, hipStream_t s, size_t scratch_bytes, size_t small_bytes, size_t pinned_bytes, NlmTables tables = NlmTables::kDrop)
+    {
+        lock_on(c, s);
+        return grow(scratch_bytes, small_bytes, pinned_bytes, tables);
     }
     ~WorkScope() { if (acquired_) (void)hipEventRecord(ctx->last_use, stream); }   // (lk_ is released after this body)
     template <typename T = uint8_t> T* scratch() const { return static_cast<T*>(ctx->scratch); }
@@ -231,34 +251,6 @@ struct DrainOnExit {
     hipStream_t s;
     ~DrainOnExit() { (void)hipStreamSynchronize(s); }
 };
-// One host page through a device stage, the path of the single-page *_host entries: under stage_mu the cached staging area
-// holds [in | out] at 256-byte offsets; `src` (in_rows rows of in_row bytes) goes up, then
-//     int run(const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t stream)
-// runs the stage on the null stream, and out_rows rows of out_row bytes come down into `dst`.
-template <typename Run>
-int stage_host_page(const uint8_t* src, size_t src_step, size_t in_row, int in_rows, uint8_t* dst, size_t dst_step,
-                    size_t out_row, int out_rows, Run&& run)
-{
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    const size_t in_bytes = r256(in_row * (size_t)in_rows), out_bytes = r256(out_row * (size_t)out_rows);
-    std::lock_guard<std::mutex> slk(ctx->stage_mu);  // cached device + pinned staging: no allocation per page (lock order: stage_mu, then mu)
-    st = ensure_stage(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
-    if (st != PRL_OK) return st;
-    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
-    uint8_t* d_out = d_in + in_bytes;
-    const hipStream_t stream = nullptr;
-    DrainOnExit drain_guard{stream};
-    st = stage_upload(ctx, 0, src, src_step, in_row, in_rows, d_in, stream);
-    if (st != PRL_OK) return st;
-    st = run(d_in, in_bytes, d_out, out_bytes, stream);
-    if (st != PRL_OK) return st;
-    return stage_download(ctx, in_bytes, d_out, out_row, out_rows, dst, dst_step, stream);
-}
 
 // ---- page addressing: contiguous batch or table of page pointers ---------------------------------
 struct PageSet {
@@ -297,18 +289,34 @@ inline Set pages_from(Set s, int first)
 inline PageSet src_pages(const PageArgs& a, int first) { return pages_from(page_set(a.src, a.src_page_stride, a.src_step), first); }
 inline PageSetOut dst_pages(const PageArgs& a, int first) { return pages_from(page_set_out(a.dst, a.dst_page_stride, a.dst_step), first); }
 
-// A *_host stage entry after its checks: the page `h` describes (host pointers; in_channels / out_channels bytes per pixel, the
-// result out_width x out_height) goes through stage_host_page, and
+// A single-page *_host stage entry after its checks: the page `h` describes (host pointers; in_channels / out_channels bytes per
+// pixel, the result out_width x out_height) goes through the device.  Under stage_mu the cached staging area holds [in | out] at
+// 256-byte offsets, rows packed tightly; the source goes up, then
 //     int run(const PageArgs& page, hipStream_t stream)
-// gets the staging area as a one-page batch of the same width and height.
+// gets the staging area as a one-page batch of the same width and height on the null stream, and the result comes down into h.dst.
 template <typename Run>
 int stage_host_pages(const PageArgs& h, int in_channels, int out_channels, int out_width, int out_height, Run&& run)
 {
+    int dev;
+    int st = current_device(&dev);
+    if (st != PRL_OK) return st;
+    DeviceCtx* ctx = device_ctx(dev);
     const size_t in_row = (size_t)h.width * in_channels, out_row = (size_t)out_width * out_channels;
-    return stage_host_page(h.src, h.src_step, in_row, h.height, h.dst, h.dst_step, out_row, out_height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return run(PageArgs{1, d_in, in_bytes, in_row, h.width, h.height, d_out, out_bytes, out_row}, s);
-                           });
+    const size_t in_bytes = r256(in_row * (size_t)h.height), out_bytes = r256(out_row * (size_t)out_height);
+    std::lock_guard<std::mutex> slk(ctx->stage_mu);  // cached device + pinned staging: no allocation per page (lock order: stage_mu, then mu)
+    st = ensure_stage(ctx, in_bytes + out_bytes);
+    if (st != PRL_OK) return st;
+    st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
+    if (st != PRL_OK) return st;
+    uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
+    uint8_t* d_out = d_in + in_bytes;
+    const hipStream_t stream = nullptr;
+    DrainOnExit drain_guard{stream};
+    st = stage_upload(ctx, 0, h.src, h.src_step, in_row, h.height, d_in, stream);
+    if (st != PRL_OK) return st;
+    st = run(PageArgs{1, d_in, in_bytes, in_row, h.width, h.height, d_out, out_bytes, out_row}, stream);
+    if (st != PRL_OK) return st;
+    return stage_download(ctx, in_bytes, d_out, out_row, out_height, h.dst, h.dst_step, stream);
 }
 
 // Threshold constants shared by the literal and fused kernels (host-prepared, passed by value).
@@ -392,7 +400,8 @@ int fused_max_pages(const ThrParams& tp);  // pages one fused_run call can take 
 int thin_batch_device(int method, int n_pages, const PageSet& src, int width, int height, const PageSetOut& dst, void* stream,
                       bool invert_input);
 
-// ---- prl::denoise in three parts (nlm.hip; the chain separates its streaming parts from its compute part) ----------------
+// ---- prl::denoise in three parts (nlm.hip; the chain separates its streaming parts from its compute part), each one
+// WorkScope on ctx ----------------
 size_t denoise_plane_bytes(int width, int height);   // per page: L, ab, L', ab'
 int denoise_convert_in(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, uint8_t* planes, hipStream_t s);
 int denoise_nlm(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int width, int height, hipStream_t s);
@@ -429,7 +438,7 @@ int deskew_find(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int w
 // dark pixels (<= the page's Otsu threshold) per page = the points HoughLinesP will visit; takes ctx->ppht_mu, synchronises hs
 int deskew_ink_census(DeviceCtx* ctx, int n_pages, int channels, const PageSet& src, int width, int height,
                       std::vector<unsigned>* points, hipStream_t hs);
-// prl::rotate of every page by its angle (copy where none was found); takes ctx->mu
+// prl::rotate of every page by its angle (copy where none was found); one WorkScope on ctx
 int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, const PageSet& src, int width, int height,
                  const PageSetOut& dst, hipStream_t hs);
 int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, const PageSetOut& dst,

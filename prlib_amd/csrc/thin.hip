@@ -267,86 +267,57 @@ __global__ void k_thin_endpass(unsigned* changed, unsigned* done, int n_pages)
     }
 }
 
-}  // namespace
-}  // namespace prl_hip
+// The launch geometry and scratch layout of a chunk of n_pages pages: one launch per pass, strips of 60 words x segments of
+// rows, one wavefront each.
+struct ThinPlan {
+    int wpr, n_strips, rps, n_segs;
+    size_t plane_words, bits_bytes, flags_bytes, act_cap;
+    unsigned long long tw;   // tiles
+    size_t scratch_bytes() const { return 2 * bits_bytes + 2 * flags_bytes + 2 * act_cap; }
+};
 
-using namespace prl_hip;
-
-extern "C" {
-
-int prl_hip_thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
-                              int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
+ThinPlan thin_plan(int n_pages, int width, int height)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;  // "Input image for thinning is empty" (thinZhangSuen.cpp:59-62)
-    if (method != PRL_THIN_ZHANGSUEN && method != PRL_THIN_GUOHALL) return PRL_ERR_BAD_ARG;
-    if (n_pages < 0 || !d_src || !d_dst || src_step < (size_t)width || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    if (n_pages == 0) return PRL_OK;
-    return prl_hip::thin_batch_device(method, n_pages, page_set(d_src, src_page_stride, src_step), width, height,
-                                      page_set_out(d_dst, dst_page_stride, dst_step), stream, false);
+    ThinPlan t{};
+    t.wpr = (width + 31) / 32;
+    t.plane_words = (size_t)t.wpr * height;
+    t.bits_bytes = t.plane_words * sizeof(unsigned) * (size_t)n_pages;
+    t.flags_bytes = r256((size_t)n_pages * sizeof(unsigned));
+    t.n_strips = (t.wpr + kThinUseful - 1) / kThinUseful;
+    t.rps = 256;  // measured (16 A4 pages): 32 rows 31 us per pass, 16: 26, 8: 26, 4: 31
+    while (t.rps > 16 && (long long)n_pages * t.n_strips * ((height + t.rps - 1) / t.rps) < 16384) t.rps /= 2;
+    if (env_knobs().thin_rps) t.rps = env_knobs().thin_rps;
+    t.n_segs = (height + t.rps - 1) / t.rps;
+    t.tw = (unsigned long long)n_pages * t.n_strips * t.n_segs;
+    t.act_cap = r256((size_t)t.tw);  // one activity byte per tile and pass parity
+    return t;
 }
 
-}  // extern "C"
-
-namespace prl_hip {
-int thin_batch_device(int method, int n_pages, const PageSet& ps, int width, int height, const PageSetOut& pd, void* stream,
-                      bool invert_input)
+// one chunk: the planes of its pages at the head of scratch, the flag readback through pinned memory
+int thin_chunk(const WorkScope& w, const ThinPlan& t, int method, int n_pages, const PageSet& ps, int width, int height,
+               const PageSetOut& pd, bool invert_input)
 {
-    if (n_pages > 32768) {  // the page index sits in a grid dimension limited to 65535
-        for (int first = 0; first < n_pages; first += 32768) {
-            const int st2 = thin_batch_device(method, std::min(32768, n_pages - first), pages_from(ps, first), width, height,
-                                              pages_from(pd, first), stream, invert_input);
-            if (st2 != PRL_OK) return st2;
-        }
-        return PRL_OK;
-    }
-    int dev;
-    int st = current_device(&dev);
-    if (st != PRL_OK) return st;
-    DeviceCtx* ctx = device_ctx(dev);
-    std::lock_guard<std::mutex> lk(ctx->mu);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const hipStream_t s = w.stream;
+    auto* A = w.scratch<unsigned>();
+    auto* B = A + t.plane_words * (size_t)n_pages;
+    auto* changed = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(B) + t.bits_bytes);
+    auto* done = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(changed) + t.flags_bytes);
+    PRL_HIP_CHECK(hipMemsetAsync(changed, 0, 2 * t.flags_bytes, s));
+    auto* act0 = reinterpret_cast<unsigned char*>(done) + t.flags_bytes;
+    auto* act1 = act0 + t.act_cap;
+    PRL_HIP_CHECK(hipMemsetAsync(act0, 1, t.act_cap, s));  // before the first pass every tile counts as changed
 
-    const int wpr = (width + 31) / 32;
-    const size_t plane_words = (size_t)wpr * height;
-    if (plane_words >= 0x7fffff00ull) return PRL_ERR_BAD_ARG;  // kernels index a page's words with 32 bits
-    const size_t bits_bytes = plane_words * sizeof(unsigned) * (size_t)n_pages;
-    const size_t flags_bytes = r256((size_t)n_pages * sizeof(unsigned));
-    // one launch per pass: strips of 60 words x segments of rows, one wavefront each
-    const int n_strips = (wpr + kThinUseful - 1) / kThinUseful;
-    int rps = 256;  // measured (16 A4 pages): 32 rows 31 us per pass, 16: 26, 8: 26, 4: 31
-    while (rps > 16 && (long long)n_pages * n_strips * ((height + rps - 1) / rps) < 16384) rps /= 2;
-    if (env_knobs().thin_rps) rps = env_knobs().thin_rps;
-    const int n_segs = (height + rps - 1) / rps;
-    const unsigned long long tw = (unsigned long long)n_pages * n_strips * n_segs;
-    if (tw >= 0xfffffff0ull) return PRL_ERR_BAD_ARG;
-    const size_t act_cap = r256((size_t)tw);  // one activity byte per tile and pass parity
-    st = ensure_scratch(ctx, 2 * bits_bytes + 2 * flags_bytes + 2 * act_cap);
-    if (st != PRL_OK) return st;
-    st = device_acquire(ctx, s);
-    if (st != PRL_OK) return st;
-    DeviceRelease release{ctx, s};
-    auto* A = static_cast<unsigned*>(ctx->scratch);
-    auto* B = A + plane_words * (size_t)n_pages;
-    auto* changed = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(B) + bits_bytes);
-    auto* done = reinterpret_cast<unsigned*>(reinterpret_cast<uint8_t*>(changed) + flags_bytes);
-    PRL_HIP_CHECK(hipMemsetAsync(changed, 0, 2 * flags_bytes, s));
-    auto* act0 = reinterpret_cast<unsigned char*>(done) + flags_bytes;
-    auto* act1 = act0 + act_cap;
-    PRL_HIP_CHECK(hipMemsetAsync(act0, 1, act_cap, s));  // before the first pass every tile counts as changed
-
-    const dim3 gw((unsigned)((plane_words + 255) / 256), n_pages);  // one thread per 32-pixel word
-    hipLaunchKernelGGL(k_thin_pack, gw, dim3(256), 0, s, ps, width, height, wpr, A, plane_words, invert_input ? 0xffffffffu : 0u);
+    const dim3 gw((unsigned)((t.plane_words + 255) / 256), n_pages);  // one thread per 32-pixel word
+    hipLaunchKernelGGL(k_thin_pack, gw, dim3(256), 0, s, ps, width, height, t.wpr, A, t.plane_words, invert_input ? 0xffffffffu : 0u);
     PRL_HIP_CHECK(hipGetLastError());
 
-    st = ensure_pinned(ctx, sizeof(unsigned) * (size_t)n_pages);  // flag readback through pinned memory
-    if (st != PRL_OK) return st;
-    unsigned* h_done = static_cast<unsigned*>(ctx->pinned);
+    unsigned* h_done = w.pinned<unsigned>();
     // No cap on the number of passes: the reference loops until a pass changes nothing (thinZhangSuen.cpp:93-104), and a
     // 2-pixel diagonal stroke erodes from its ends only, about a row per pass (max(W,H)+2 was an unproven bound
     // that returned a non-converged plane).  Every effective pass removes at least one pixel, so the loop ends.
     int group = 4;  // passes per host check, doubled each time (a pass over converged pages / idle tiles is nearly free)
     const unsigned wpb = (unsigned)env_knobs().thin_wpb;
-    const dim3 gp((unsigned)((tw + wpb - 1) / wpb)), bp(64 * wpb);  // short wavefronts: 4 per workgroup measured best (26.1 vs 28.4 us)
+    const dim3 gp((unsigned)((t.tw + wpb - 1) / wpb)), bp(64 * wpb);  // short wavefronts: 4 per workgroup measured best (26.1 vs 28.4 us)
     // Passes alternate A -> B -> A.  The pass that finds a page unchanged has just written a copy of its input, so
     // from then on BOTH buffers hold that page's final plane (later passes skip it): k_thin_unpack can always read A.
     for (int pass = 0;;) {
@@ -356,11 +327,11 @@ int thin_batch_device(int method, int n_pages, const PageSet& ps, int width, int
             const unsigned char* act_prev = (pass & 1) ? act1 : act0;
             unsigned char* act_cur = (pass & 1) ? act0 : act1;
             if (method == PRL_THIN_ZHANGSUEN)
-                hipLaunchKernelGGL(k_thin_pass<0>, gp, bp, 0, s, in, out, plane_words, wpr, width, height, n_strips,
-                                   n_segs, rps, (unsigned)tw, changed, done, act_prev, act_cur);
+                hipLaunchKernelGGL(k_thin_pass<0>, gp, bp, 0, s, in, out, t.plane_words, t.wpr, width, height, t.n_strips,
+                                   t.n_segs, t.rps, (unsigned)t.tw, changed, done, act_prev, act_cur);
             else
-                hipLaunchKernelGGL(k_thin_pass<1>, gp, bp, 0, s, in, out, plane_words, wpr, width, height, n_strips,
-                                   n_segs, rps, (unsigned)tw, changed, done, act_prev, act_cur);
+                hipLaunchKernelGGL(k_thin_pass<1>, gp, bp, 0, s, in, out, t.plane_words, t.wpr, width, height, t.n_strips,
+                                   t.n_segs, t.rps, (unsigned)t.tw, changed, done, act_prev, act_cur);
             PRL_HIP_CHECK(hipGetLastError());
             hipLaunchKernelGGL(k_thin_endpass, dim3((n_pages + 255) / 256), dim3(256), 0, s, changed, done, n_pages);
             PRL_HIP_CHECK(hipGetLastError());
@@ -370,24 +341,62 @@ int thin_batch_device(int method, int n_pages, const PageSet& ps, int width, int
         if (std::all_of(h_done, h_done + n_pages, [](unsigned v) { return v != 0; })) break;
         group = std::min(group * 2, 32);
     }
-    const dim3 gu((unsigned)(((size_t)(wpr + 1) * height + 255) / 256), n_pages);  // one thread per aligned 32-byte block
-    hipLaunchKernelGGL(k_thin_unpack, gu, dim3(256), 0, s, A, plane_words, wpr, pd, width, height);
+    const dim3 gu((unsigned)(((size_t)(t.wpr + 1) * height + 255) / 256), n_pages);  // one thread per aligned 32-byte block
+    hipLaunchKernelGGL(k_thin_unpack, gu, dim3(256), 0, s, A, t.plane_words, t.wpr, pd, width, height);
     PRL_HIP_CHECK(hipGetLastError());
+    return PRL_OK;
+}
+}  // namespace
+
+int thin_batch_device(int method, int n_pages, const PageSet& ps, int width, int height, const PageSetOut& pd, void* stream,
+                      bool invert_input)
+{
+    WorkScope w;
+    int st = w.lock(stream);
+    if (st != PRL_OK || n_pages <= 0) return st;
+    // The page index sits in a grid dimension limited to 65535.  A batch runs as full chunks and one shorter last chunk; each
+    // has the geometry of a batch of that many pages (fewer pages may mean shorter row segments, hence more activity bytes),
+    // and both are refused or sized here, before anything is allocated or enqueued.
+    const int chunk = stage_chunk(n_pages, 0, 0, 32768), last = n_pages % chunk ? n_pages % chunk : chunk;
+    const ThinPlan full = thin_plan(chunk, width, height), tail = thin_plan(last, width, height);
+    if (full.plane_words >= 0x7fffff00ull) return PRL_ERR_BAD_ARG;  // kernels index a page's words with 32 bits
+    if (full.tw >= 0xfffffff0ull || tail.tw >= 0xfffffff0ull) return PRL_ERR_BAD_ARG;
+    st = w.grow(std::max(full.scratch_bytes(), tail.scratch_bytes()), 0, sizeof(unsigned) * (size_t)chunk);
+    if (st != PRL_OK) return st;
+    for (int first = 0; first < n_pages; first += chunk) {
+        const int cnt = std::min(chunk, n_pages - first);
+        st = thin_chunk(w, cnt == chunk ? full : tail, method, cnt, pages_from(ps, first), width, height, pages_from(pd, first), invert_input);
+        if (st != PRL_OK) return st;
+    }
     return PRL_OK;
 }
 }  // namespace prl_hip
 
+using namespace prl_hip;
+
 extern "C" {
+
+int prl_hip_thin_batch_device(int method, int n_pages, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                              int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
+{
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    int st = pages_nonempty(a);  // "Input image for thinning is empty" (thinZhangSuen.cpp:59-62)
+    if (st != PRL_OK) return st;
+    if (method != PRL_THIN_ZHANGSUEN && method != PRL_THIN_GUOHALL) return PRL_ERR_BAD_ARG;
+    if ((st = pages_rows_ok(a, 1, 1, true)) != PRL_OK) return st;
+    if (n_pages == 0) return PRL_OK;
+    return thin_batch_device(method, n_pages, src_pages(a, 0), width, height, dst_pages(a, 0), stream, false);
+}
 
 int prl_hip_thin_host(int method, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
 {
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (!src || !dst || src_step < (size_t)width || dst_step < (size_t)width) return PRL_ERR_BAD_ARG;
-    const size_t row = (size_t)width;
-    return stage_host_page(src, src_step, row, height, dst, dst_step, row, height,
-                           [&](const uint8_t* d_in, size_t in_bytes, uint8_t* d_out, size_t out_bytes, hipStream_t s) {
-                               return prl_hip_thin_batch_device(method, 1, d_in, in_bytes, row, width, height, d_out, out_bytes, row, s);
-                           });
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
+    if ((st = pages_rows_ok(a, 1, 1, false)) != PRL_OK) return st;
+    return stage_host_pages(a, 1, 1, width, height, [&](const PageArgs& p, hipStream_t s) {
+        return prl_hip_thin_batch_device(method, 1, p.src, p.src_page_stride, p.src_step, width, height, p.dst, p.dst_page_stride, p.dst_step, s);
+    });
 }
 
 }  // extern "C"

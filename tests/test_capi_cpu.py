@@ -156,7 +156,7 @@ def test_entry_statuses_without_a_device(prl):
                                                   dps=ps, ds=12, stream=None), [
             (dict(w=0), EMPTY), (dict(n=-1), ARG), (dict(src=None), ARG), (dict(dst=None), ARG), (dict(ss=35), ARG),
             (dict(ds=11), ARG), (dict(h=1048561), ARG), (dict(n=0), OK), (dict(w=0, n=-1), EMPTY), (dict(n=0, h=1048561), ARG),
-            (dict(), NODEV), (dict(wf=0), NODEV), (dict(h=1048560), NODEV)]),
+            (dict(w=0, src=None), EMPTY), (dict(), NODEV), (dict(wf=0), NODEV), (dict(h=1048560), NODEV)]),
         (L.prl_hip_thin_batch_device, dict(m=0, n=1, src=s, sps=ps, ss=12, w=12, h=8, dst=d, dps=ps, ds=12, stream=None), [
             (dict(w=0), EMPTY), (dict(m=2), ARG), (dict(m=-1), ARG), (dict(n=-1), ARG), (dict(src=None), ARG),
             (dict(dst=None), ARG), (dict(ss=11), ARG), (dict(ds=11), ARG), (dict(n=0), OK),

@@ -14,8 +14,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_five_pages_in_chunks_of_two(prl, cuda_device):
     """Every batched result is byte for byte the stack of the five single-page calls of the same process (one page is one chunk
-    whatever the knob says); median, removeLines and the tone functions also equal their restatements.  All outputs are
-    integers: zero differing bytes, no tolerance."""
+    whatever the knob says); median, removeLines and the tone functions also equal their restatements.  Thinning, the
+    local-variance binarizers, denoise, backgroundNormalization, the mask morphology (fused and large radius) and rotate go
+    through their C entries on the strided pages, on inputs whose results are neither constant nor equal between pages.  All outputs are integers: zero differing bytes, no tolerance."""
     code = r'''
 import sys, numpy as np
 sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
@@ -89,6 +90,89 @@ for c in (1, 3):
         sizes.add(tuple(one.shape[:2]))
     assert len(sizes) > 1   # the pages' results differ in size
     checked.append("warp_crop c=%d" % c)
+
+# The older entries, straight through the C ABI (some of their Python wrappers take dense tensors only): thinning, the
+# local-variance binarizers, denoise, backgroundNormalization, the mask morphology and rotate.
+L = _capi.lib()
+
+def entry(fn, head, pages, out_channels):
+    """fn(*head(n), src, page stride, step, w, h, dst, page stride, step, stream) on n strided pages -> n x H x W x out_channels"""
+    n, h, w = pages.shape[:3]
+    out = torch.zeros((n, h, w, out_channels), dtype=torch.uint8, device="cuda")
+    _capi.check(fn(*head(n), pages.data_ptr(), pages.stride(0), pages.stride(1), w, h, out.data_ptr(), out.stride(0), out.stride(1),
+                   _capi.stream_on(pages)))
+    return out
+
+def each_entry(name, fn, head, pages, out_channels, varied=True):
+    """varied: no page's result is constant and no two pages' results are equal, so a chunk that read another page, or another
+    page's thresholds or work plane, cannot give the same bytes"""
+    assert pages.stride(0) > H * pages.stride(1) and pages.stride(1) > W * (pages.shape[3] if pages.dim() == 4 else 1)
+    singles = [entry(fn, head, pages[i:i + 1], out_channels)[0] for i in range(N)]
+    if varied:
+        assert all(int(r.min()) != int(r.max()) for r in singles), (name, "a constant result")
+        assert len({r.cpu().numpy().tobytes() for r in singles}) == N, (name, "two pages with the same result")
+    same(name, entry(fn, head, pages, out_channels), singles)
+
+def recut(t):
+    """the same pages inside a larger buffer again"""
+    big = torch.zeros((N, H + 16, W + 16) + tuple(t.shape[3:]), dtype=torch.uint8, device="cuda")
+    big[:, 3:3 + H, 5:5 + W] = t
+    return big[:, 3:3 + H, 5:5 + W]
+
+colour4 = cut(4)
+black_white = recut(torch.where(gray > 127, 255, 0).to(torch.uint8))   # the rules of cut() are black: another skeleton on every page
+for c, pages in ((3, colour), (4, colour4)):
+    each_entry("denoise c=%d" % c, L.prl_hip_denoise_batch_device, lambda n: (n, c, 10.0), pages, c)
+for method, name in ((0, "thinZhangSuen"), (1, "thinGuoHall")):
+    each_entry(name, L.prl_hip_thin_batch_device, lambda n: (method, n), black_white, 1)
+each_entry("binarizeByLocalVariances", L.prl_hip_binarize_lv_batch_device, lambda n: (n, 1, 0.125, 25, 2.0), colour, 1)
+# (on the noise of cut() every pixel passes the unfiltered variant's two tests: five white masks, which show a wrong destination only)
+each_entry("binarizeByLocalVariancesWithoutFilters", L.prl_hip_binarize_lv_batch_device, lambda n: (n, 0, 0.125, 10, 2.0), colour, 1, varied=False)
+import lv_ref
+text = recut(torch.from_numpy(np.stack([lv_ref.colour(H, W, 40 + i) for i in range(N)])).cuda())   # smooth paper and strokes: masks of both values
+each_entry("binarizeByLocalVariances, text", L.prl_hip_binarize_lv_batch_device, lambda n: (n, 1, 0.125, 25, 2.0), text, 1)
+each_entry("binarizeByLocalVariancesWithoutFilters, text", L.prl_hip_binarize_lv_batch_device, lambda n: (n, 0, 0.125, 10, 2.0), text, 1)
+for c, pages in ((1, gray), (3, colour)):
+    each_entry("backgroundNormalization c=%d" % c, L.prl_hip_bgnorm_batch_device, lambda n: (n, c), pages, c)
+
+def blobs():
+    """masks that are mostly 0, another on every page: two 20 x 30 rectangles 2, 6, ... 18 columns apart (a closing of radius 2 or 9
+    bridges some of the gaps), a hole, squares of 3 and 7 and a rule 1 ... 5 rows thick (an opening of radius 9 removes them)"""
+    m = np.zeros((N, H, W), np.uint8)
+    for i in range(N):
+        gap = 2 + 4 * i
+        m[i, 4 + 2 * i:34 + 2 * i, 2:22] = 255
+        m[i, 4 + 2 * i:34 + 2 * i, 22 + gap:42 + gap] = 255
+        m[i, 10 + 2 * i:11 + 3 * i, 8:9 + i] = 0
+        m[i, 50 + i:53 + i, 5 + 9 * i:8 + 9 * i] = 255
+        m[i, 58:65, 6 + 8 * i:13 + 8 * i] = 255
+        m[i, 70:71 + i, 4:60] = 255
+    return recut(torch.from_numpy(m).cuda())
+
+masks = blobs()
+# the fused kernels (no workspace); the large-radius path, whose tmp plane restarts at each chunk, closing and opening
+for iterations in (2, 9, -9):
+    each_entry("morph %d" % iterations, L.prl_hip_morph_batch_device, lambda n: (iterations, n), masks, 1)
+
+from prlib_amd.deskew import rotate_out_size
+angles = np.array([0.0, 90.0, 7.5, -13.0, 181.0])
+
+def rotate(pages, ang):
+    n, h, w = pages.shape[:3]
+    c = pages.shape[3] if pages.dim() == 4 else 1
+    sizes = [rotate_out_size(w, h, a) for a in ang]
+    buf = torch.zeros((n, max(s[1] for s in sizes), max(s[0] for s in sizes), c), dtype=torch.uint8, device="cuda")
+    _capi.check(L.prl_hip_rotate_batch_device(n, c, ang.ctypes.data, pages.data_ptr(), pages.stride(0), pages.stride(1), w, h,
+                                              buf.data_ptr(), buf.stride(0), buf.stride(1), _capi.stream_on(pages)))
+    return [buf[i, :oh, :ow] for i, (ow, oh) in enumerate(sizes)]
+
+for c, pages in ((1, gray), (3, colour)):
+    got = rotate(pages, angles)
+    for i in range(N):
+        one = rotate(pages[i:i + 1], angles[i:i + 1])[0]
+        assert got[i].shape == one.shape and torch.equal(got[i], one), ("rotate", c, i, int((got[i] != one).sum()))
+    assert len(set(tuple(g.shape[:2]) for g in got)) > 1   # the pages' results differ in size
+    checked.append("rotate c=%d" % c)
 
 torch.cuda.synchronize()
 print("stage chunks ok: %d comparisons" % len(checked))

@@ -1,6 +1,9 @@
-"""Host time per call of two stage entries on one 64 x 64 gray page, where the kernels are a few microseconds and what is
-measured is the entry's own code: prl_hip_lut_batch_device (checks and a launch: no workspace, no lock) and
-prl_hip_median_batch_device(k = 3, times = 1) (checks, the shared workspace's lock and acquire, a launch).
+"""Host time per call of four stage entries on one 64 x 64 gray page, where the kernels are a few microseconds and what is
+measured is the entry's own code: prl_hip_lut_batch_device (checks and a launch: no workspace, no lock),
+prl_hip_median_batch_device(k = 3, times = 1) (checks, the shared workspace's lock and acquire, a launch),
+prl_hip_nlm_planes_device(1 channel, h = 10) (checks, the workspace, the weight table cached from the call before, a launch: a
+table rebuilt and uploaded per call would show here) and prl_hip_morph_batch_device(9 iterations) (checks, the workspace with a
+scratch plane, the large-radius launches).
 
     python tools/bench_stage_entry.py [--lib PATH] [--calls 4000] [--repeats 5]
 
@@ -38,6 +41,8 @@ def main():
     entries = {
         "lut": lambda: L.prl_hip_lut_batch_device(n, 1, t, 0, s, w * h, w, w, h, d, w * h, w, stream),
         "median3": lambda: L.prl_hip_median_batch_device(n, 1, 3, 1, s, w * h, w, w, h, d, w * h, w, stream),
+        "nlm_planes": lambda: L.prl_hip_nlm_planes_device(n, 1, 10.0, s, w * h, w, w, h, d, w * h, w, stream),
+        "morph9": lambda: L.prl_hip_morph_batch_device(9, n, s, w * h, w, w, h, d, w * h, w, stream),
     }
     for name, call in entries.items():
         for _ in range(200):   # warm-up: code objects, the workspace
