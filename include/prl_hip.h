@@ -416,6 +416,23 @@ int prl_hip_morphology_host(int channels, int op, int shape, int ksize_w, int ks
                             int height, uint8_t* dst, size_t dst_step);
 
 /*
+ * cv::morphologyEx(src, dst, op, element, Point(anchor_x, anchor_y), iterations): the entries above with the two arguments they
+ * fix; (-1, -1, 1) is exactly them.  An anchor of -1 is the centre ksize / 2, taken per coordinate; otherwise it lies in
+ * 0 .. ksize - 1 and dst(y, x, c) = min / max of src(y + i - anchor_y, x + j - anchor_x, c).  iterations = n in 1..16
+ * [upstream, morph.cpp]: an element whose every pixel is set (a rectangle, whatever `shape` says) runs ONCE as the rectangle of
+ * 1 + n (ksize_w - 1) x 1 + n (ksize_h - 1) with the anchor (n anchor_x, n anchor_y), which equals n passes because taps outside
+ * the page are ignored and the anchor lies inside the element; a grown side above 255 is PRL_ERR_BAD_ARG.  Cross and ellipse run n
+ * real passes.  The composite operators apply n to each half: CLOSE is n dilations, then n erosions; TOPHAT and BLACKHAT subtract
+ * once, at the end.  Everything else - layouts, in place, limits, stream semantics - as above; the anchor and iterations are
+ * checked with the element (PRL_ERR_BAD_ARG, second in the order).
+ */
+int prl_hip_morphology_ex_batch_device(int n_pages, int channels, int op, int shape, int ksize_w, int ksize_h, int anchor_x, int anchor_y,
+                                       int iterations, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
+                                       uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_morphology_ex_host(int channels, int op, int shape, int ksize_w, int ksize_h, int anchor_x, int anchor_y, int iterations,
+                               const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+
+/*
  * prl::correctNUIL(in, out, structuringElementSize = 31) (src/correctNUIL.cpp:33-90): per page and channel, the channel is
  * inverted (x ^ 255) where its mean over the page is below 128 (decided on the device as sum < 128 * width * height), then
  * dst = 255 - blackhat(channel, ellipse(size, size)).  Same layouts, aliasing rule, limits, stream semantics and order of the
@@ -859,8 +876,8 @@ int prl_hip_warp_crop_host(int channels, const int32_t quad[8], double ratio, co
  * (longSide from the reduced size each time; 511 gives no level), the channel with the first maximum of cv::meanStdDev's
  * standard deviations, cv::Canny(25, 50) on it.  The deviations come from the last level's per-channel histograms, on the host in
  * float64: mean = sum(h v) / N, stddev = sqrt(max(sum(h v^2) / N - mean^2, 0)), both sums exact integers: ONE small read-back
- * (the bins) per chunk of pages, before the edge map.  Gray pages skip it.  The retries of autoCrop.cpp:118-125 and the contour
- * search are not provided.
+ * (the bins) per chunk of pages, before the edge map.  Gray pages skip it.  The quad search on this map and the retry of
+ * autoCrop.cpp:118-125 are the next section ("document contour").
  *
  * prl::resize (resize.cpp:29-62).  Pyramid path (scaleX or scaleY not positive): pyrDown while the long side exceeds maxSize;
  * maxSize < 1 never ends in the reference and is PRL_ERR_BAD_ARG here.  Scale path: cv::resize(INTER_AREA) to cols * scaleX x
@@ -918,6 +935,96 @@ int prl_hip_resize_replicate_batch_device(int n_pages, int channels, int scale_x
                                           void* stream);
 int prl_hip_resize_replicate_host(int channels, int scale_x, int scale_y, const uint8_t* src, size_t src_step, int width, int height,
                                   uint8_t* dst, size_t dst_step);
+
+/* ---- document contour (prl::documentContour, prl::autoCrop: autoCrop.cpp:43-175, autoCropUtils.cpp:40-55, 141-348) ---------- */
+
+/*
+ * prl::documentContour finds the page in a photograph as four corners: the edge map above, findDocumentContour on it, one retry
+ * after a closing, scaleContour and cropVerticesOrdering.  The pixel work runs on the device; the search runs on the host, per
+ * page, on a map of at most 511 x 511 pixels, in the arithmetic below ([upstream]: OpenCV's contours.cpp, approx.cpp, shapedescr.cpp,
+ * convhull.cpp of 3.4 / 4.x before the 4.10 rewrite of findContours), as restated in tests/contour_ref.py.  Parity with an
+ * installed OpenCV is not pinned.
+ *
+ * cv::findContours(map, RETR_CCOMP, CHAIN_APPROX_SIMPLE) [upstream: Suzuki-Abe].  Non-zero is foreground (value 1).  The page is
+ * surrounded by one pixel of background and keeps its own border pixels.  The page's pixels are scanned in raster order, `prev`
+ * being the value to the left (0 at a row's start) and `p` the pixel's own:
+ *     an outer border starts at a pixel with p == 1 (foreground, unmarked) and prev == 0;
+ *     a hole border starts at the pixel to the LEFT of a page pixel with p == 0 whose own value is 1 or 2, that is foreground and
+ *     not marked as a right-hand end (so the scan never starts a hole border from the last column's right side);
+ *     after a border the scan goes on from the same pixel with the value it has now.
+ * Directions: 0 = (+1, 0), 1 = (+1, -1), 2 = (0, -1), 3 = (-1, -1), 4 = (-1, 0), 5 = (-1, +1), 6 = (0, +1), 7 = (+1, +1).  From the
+ * start pixel i0 the first neighbour i1 is searched clockwise, s = 3, 2, 1, 0, 7, 6, 5 for an outer border (from 4) and
+ * s = 7, 6, ..., 1 for a hole border (from 0); none: an isolated pixel, marked as a right-hand end, one point.  Else, with i3 = i0 and
+ * the arrival direction s: the next neighbour i4 is the first non-zero one counter-clockwise from s + 1 (s + 1, s + 2, ... mod 8);
+ * with s' its direction, i3 is marked as a right-hand end (-126) if (unsigned)(s' - 1) < (unsigned)s, else 2 if it still was 1;
+ * the point i3 is emitted iff s' differs from the direction of the step before (initially the first s with bit 2 flipped, s ^ 4);
+ * the walk ends when i4 == i0 and i3 == i1, else i3 = i4, s = (s' + 4) mod 8.  Points are page coordinates.
+ * Order of the result: outer borders from the last discovered to the first, each followed by the hole borders of its 8-connected
+ * component, last discovered first (OpenCV hangs a hole on the outer border that surrounds it, which is that one).  Both kinds are
+ * candidates; the order decides ties only.
+ *
+ * cv::approxPolyDP(points, eps, closed = true) on integer points [upstream], eps2 = eps * eps, all distances in float64:
+ *     1. three rounds: from the current start (first: point 0) the point of largest squared distance, the first of equals; the next
+ *        round starts there.  If the last round's largest squared distance is <= eps2 the result is that round's start alone.
+ *     2. else the slices (start, far) and (far, start) of the last round go on a stack, the first on top.
+ *     3. a slice (a, b) is popped; with chord d = P[b] - P[a], the point between them of largest |(y - ya) dx - (x - xa) dy|, first
+ *        of equals; if there is none, or that value squared is <= eps2 * (dx^2 + dy^2), P[a] is written, else (far, b) and then
+ *        (a, far) are pushed.
+ *     4. clean-up over the written points, cyclically from the last one (start S), P the next, E the one after: with d = E - S,
+ *        P is dropped iff |(Px - Sx) dy - (Py - Sy) dx|^2 <= 0.5 eps2 (dx^2 + dy^2) and dx != 0 and dy != 0 and
+ *        (P - S).(E - P) >= 0; then S = E and the walk skips one; else S = P.  It stops at two points.
+ * The reference feeds each result back in with eps = 1, 2, 3, ... until at most 4 points remain (autoCropUtils.cpp:186-191).
+ *
+ * A polygon of exactly four points p0..p3 is a candidate iff (autoCropUtils.cpp:193-235), in float64:
+ *     area = |sum(x[i-1] y[i] - x[i] y[i-1])| / 2, i from 0 with i - 1 = 3 first             (cv::contourArea)
+ *     side1..4 = |p0 p1|, |p1 p2|, |p2 p3|, |p3 p0|, sqrt of the float64 sum of squares       (cv::norm)
+ *     min(side1, side3) / max(side1, side3) >= 0.85 and likewise for sides 2, 4 (stated as "not < 0.85": a NaN passes)
+ *     angle(p0, p1, p2, p3) >= 160 and angle(p1, p2, p3, p0) >= 160, where angle(a, b, c, d) =
+ *         r = (atan2(cy - dy, cx - dx) - atan2(ay - by, ax - bx)) * 180.0 / 3.14;  r < 0: r += 360;  r > 180: r = 360 - r
+ *     area <= cols * rows (an int product) and area >= minArea, minArea = 0.05 * cols * rows at first
+ * and it replaces the kept one iff area > minArea (strictly), which then becomes minArea.  The kept polygon is the answer iff
+ * cv::convexHull of its points has four vertices, that is iff the four are in strictly convex position: decided in exact integers.
+ * The corners leave in the polygon's own order.
+ *
+ * scaleContour, cropVerticesOrdering (autoCropUtils.cpp:269-348): xScale = (float)src_w / (float)map_w, likewise y, where
+ * map_w x map_h is cols / 2^levels x rows / 2^levels (autoCrop.cpp:83, integer division: 1027 gives 513 at one level while the
+ * pyramid's map is 514 wide); x *= xScale, y *= yScale in float.  The hull's cycle is taken with
+ * sum(x[i] y[i+1] - x[i+1] y[i]) > 0 (top left -> top right -> bottom right -> bottom left on the screen), starting at the corner of
+ * smallest x, then smallest y: both decided on the integer corners, which a positive scale does not reorder.  The cycle is then
+ * rotated to the first corner of strictly smallest x * x + y * y, each product and the sum rounded to float, as written.
+ *
+ * The retry (autoCrop.cpp:105-128): a page without a quad gets cv::dilate, then cv::erode, of its map with the 2 x 2 rectangle,
+ * default anchor, iterations = 2, which is prl_hip_morphology_ex's CLOSE; then the search again.  `try` is 0 for a page found at
+ * once and 1 for every other page, found or not.  The reference closes the map once more after the second search (iterations = 3)
+ * and then returns without looking at it: that closing changes nothing observable and is not run.
+ * Positive scaleX, scaleY take cv::resize(INTER_AREA) in general position: not in the C ABI; the C++ layer throws
+ * cv::Exception(StsNotImplemented).
+ */
+
+/* cv::findContours as above, host code, no device needed.  points: x, y per point, the borders one after the other; contours: per
+ * border its number of points and 1 for a hole border.  n_points / n_contours always receive the totals; the arrays are written
+ * only if both have room (max_points points, max_contours borders).  PRL_ERR_EMPTY, then PRL_ERR_BAD_ARG (null, step < width). */
+int prl_hip_find_contours(const uint8_t* map, size_t step, int width, int height, int32_t* points, int max_points, int32_t* contours,
+                          int max_contours, int* n_points, int* n_contours);
+/* cv::approxPolyDP(closed) as above; out_points has room for n_points points.  Host code. */
+int prl_hip_approx_poly_closed(const int32_t* points, int n_points, double epsilon, int32_t* out_points, int* n_out);
+/* findDocumentContour on an 8UC1 map: *found = 1 and the four corners in the polygon's own order, or *found = 0 and zeros.  Host
+ * code, no device needed.  PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_ARG (null, step < width, a side above 32768). */
+int prl_hip_document_quad(const uint8_t* map, size_t step, int width, int height, int32_t quad[8], int* found);
+/* scaleContour, then cropVerticesOrdering.  Host code.  PRL_ERR_BAD_ARG for corners that are not in strictly convex position (the
+ * reference reads past its hull there); nothing is written then. */
+int prl_hip_document_quad_finish(const int32_t quad[8], int map_width, int map_height, int src_width, int src_height, float out[8]);
+
+/* prl::documentContour(page, -1, -1, contour) per page of 1, 3 or 4 channels in device memory.  quads (host, 8 floats per page: the
+ * ordered corners, zeros without a quad), found (host, 0 / 1 per page), out_try (host or NULL) as above.  Per chunk of pages: the
+ * edge maps, ONE copy of them to pinned host memory, the search per page on the library's host thread pool (the pool of the
+ * host-list entries: PRL_HIP_HOST_COPY_THREADS), the closing on the pages without a quad alone, as a table of pages, their copy
+ * and second search.  Waits for the stream.  Checked as the edge entries are: PRL_ERR_EMPTY; PRL_ERR_BAD_CHANNELS;
+ * PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row bytes, a side above 32768). */
+int prl_hip_document_contour_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                          int height, float* quads, int32_t* found, int32_t* out_try, void* stream);
+int prl_hip_document_contour_host(int channels, const uint8_t* src, size_t src_step, int width, int height, float quad[8], int32_t* found,
+                                  int32_t* out_try);
 
 #ifdef __cplusplus
 }

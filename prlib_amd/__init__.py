@@ -7,7 +7,7 @@ with the reference's prl::binarize*(cv::Mat&, cv::Mat&, ...) signatures lives in
 from . import _capi, binarizations  # noqa: F401
 from .denoise import denoise, denoiseSaltPepper, nlm_planes  # noqa: F401
 from .adaptive import adaptiveThreshold, binarizeAGT, binarizeAT, binarizeNativeAdaptive, binarizePureAdaptiveGaussian  # noqa: F401
-from .morphology import correctNUIL, morphologyEx  # noqa: F401
+from .morphology import correctNUIL, morphologyEx, morphology_ex  # noqa: F401
 from .lines import removeLines  # noqa: F401
 from .tone import cleanBackgroundToWhite, gammaCorrection, grayWorldWhiteBalance, histogram, lut, simpleWhiteBalance  # noqa: F401
 from .mokji import binarizeMokji, cooccurrence, mokjiThreshold, mokjiThresholds  # noqa: F401
@@ -16,7 +16,8 @@ from .background import backgroundNormalization  # noqa: F401
 from .deskew import deskew, deskew_stats, find_angle as findAngle, find_orientation as findOrientation, houghp, rotate  # noqa: F401
 from .warp import perspective_transform, warp_crop, warp_crop_host, warp_crop_size, warp_perspective  # noqa: F401
 from .edges import (canny, canny_classes, document_edges, document_edges_geometry, edge_link, pyr_down, pyr_down_size, resize,  # noqa: F401
-                    resize_pyramid_levels)
+                    resize_pyramid_levels, approx_poly_closed, auto_crop, document_contour, document_quad, document_quad_finish,
+                    find_contours)
 from .chain import bitwise_not, cvtColorBGR2GRAY, cvtColorGRAY2BGR, process_pages, process_pages_host  # noqa: F401
 from .binarizations import (  # noqa: F401
     FENG, NICK, NIBLACK, SAUVOLA, WOLFJOLION, binarize, binarizeFeng, binarizeNICK, binarizeNiblack,
@@ -27,6 +28,6 @@ from .binarizations import (  # noqa: F401
 __all__ = [
     "binarize", "binarizeSauvola", "binarizeNiblack", "binarizeWolfJolion", "binarizeNICK", "binarizeFeng", "binarizeByLocalVariances", "binarizeByLocalVariancesWithoutFilters",
     "adaptiveThreshold", "binarizeNativeAdaptive", "binarizeAT", "binarizeAGT", "binarizePureAdaptiveGaussian",
-    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize", "resize_pyramid_levels", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
+    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "morphology_ex", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize", "resize_pyramid_levels", "find_contours", "approx_poly_closed", "document_quad", "document_quad_finish", "document_contour", "auto_crop", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
     "SAUVOLA", "NIBLACK", "WOLFJOLION", "NICK", "FENG",
 ]

@@ -56,7 +56,8 @@ EXPORTED_SYMBOLS = [
     "prl_hip_median_batch_device", "prl_hip_median_host",
     "prl_hip_adaptive_threshold_batch_device", "prl_hip_adaptive_threshold_host", "prl_hip_default_adaptive_params",
     "prl_hip_binarize_adaptive_batch_device", "prl_hip_binarize_adaptive_host",
-    "prl_hip_morphology_batch_device", "prl_hip_morphology_host", "prl_hip_correct_nuil_batch_device", "prl_hip_correct_nuil_host",
+    "prl_hip_morphology_batch_device", "prl_hip_morphology_host", "prl_hip_morphology_ex_batch_device", "prl_hip_morphology_ex_host",
+    "prl_hip_correct_nuil_batch_device", "prl_hip_correct_nuil_host",
     "prl_hip_remove_lines_batch_device", "prl_hip_remove_lines_host",
     "prl_hip_histogram_batch_device", "prl_hip_lut_batch_device",
     "prl_hip_gamma_correction_batch_device", "prl_hip_gamma_correction_host",
@@ -72,6 +73,8 @@ EXPORTED_SYMBOLS = [
     "prl_hip_canny_classes_batch_device", "prl_hip_edge_link_batch_device", "prl_hip_canny_batch_device", "prl_hip_canny_host",
     "prl_hip_document_edges_geometry", "prl_hip_document_edges_batch_device", "prl_hip_document_edges_host",
     "prl_hip_resize_pyramid_levels", "prl_hip_resize_replicate_batch_device", "prl_hip_resize_replicate_host",
+    "prl_hip_find_contours", "prl_hip_approx_poly_closed", "prl_hip_document_quad", "prl_hip_document_quad_finish",
+    "prl_hip_document_contour_batch_device", "prl_hip_document_contour_host",
 ]
 
 
@@ -209,6 +212,8 @@ def lib() -> C.CDLL:
         L.prl_hip_binarize_adaptive_host.argtypes = [P(AdaptiveParams), i, vp, sz, i, i, vp, sz]
         L.prl_hip_morphology_batch_device.argtypes = [i, i, i, i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_morphology_host.argtypes = [i, i, i, i, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_morphology_ex_batch_device.argtypes = [i, i, i, i, i, i, i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_morphology_ex_host.argtypes = [i, i, i, i, i, i, i, i, vp, sz, i, i, vp, sz]
         L.prl_hip_correct_nuil_batch_device.argtypes = [i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_correct_nuil_host.argtypes = [i, i, vp, sz, i, i, vp, sz]
         L.prl_hip_remove_lines_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
@@ -250,6 +255,12 @@ def lib() -> C.CDLL:
         L.prl_hip_resize_pyramid_levels.argtypes = [i, i, i, P(C.c_int), P(C.c_int), P(C.c_int)]
         L.prl_hip_resize_replicate_batch_device.argtypes = [i, i, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_resize_replicate_host.argtypes = [i, i, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_find_contours.argtypes = [vp, sz, i, i, vp, i, vp, i, P(C.c_int), P(C.c_int)]
+        L.prl_hip_approx_poly_closed.argtypes = [vp, i, d, vp, P(C.c_int)]
+        L.prl_hip_document_quad.argtypes = [vp, sz, i, i, vp, P(C.c_int)]
+        L.prl_hip_document_quad_finish.argtypes = [vp, i, i, i, i, vp]
+        L.prl_hip_document_contour_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, vp, vp, vp]
+        L.prl_hip_document_contour_host.argtypes = [i, vp, sz, i, i, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -21,6 +21,7 @@
 #include <cstring>
 #include <vector>
 
+#include "contour.h"
 #include "prl_internal.h"
 
 namespace prl_hip {
@@ -445,7 +446,15 @@ int doc_checks(const PageArgs& a, int channels, const int32_t* out_channel, bool
     return resized_dst_ok(a, 1, ow, oh, batch);
 }
 
-int doc_batch(const PageArgs& a, int channels, int32_t* out_channel, void* stream)
+// What prl::documentContour hangs on a chunk of doc_batch: the maps stay in the workspace (a.dst is null), tight pages of
+// r256(ow * oh) bytes at the head of a tail of `scratch_per_page` bytes per page behind the edge detector's own work, and `run`
+// gets every chunk once its maps are complete and the stream has been waited for; the `small` and pinned blocks are free then.
+struct DocTail {
+    size_t scratch_per_page = 0, small_per_page = 0, pinned_per_page = 0;
+    std::function<int(int first, int n, uint8_t* tail, const WorkScope& w)> run;
+};
+
+int doc_batch(const PageArgs& a, int channels, int32_t* out_channel, void* stream, const DocTail* tail = nullptr)
 {
     if (a.n_pages == 0) return PRL_OK;
     int levels, ow, oh;
@@ -453,17 +462,21 @@ int doc_batch(const PageArgs& a, int channels, int32_t* out_channel, void* strea
     const size_t pyr_bytes = levels ? pyr_work_per_page(a.width, a.height, channels, levels) : 0;
     const size_t last_bytes = levels ? r256((size_t)ow * channels * (size_t)oh) : 0;   // the last level
     const size_t gray_bytes = channels > 1 ? r256((size_t)ow * (size_t)oh) : 0;        // the chosen channel
-    const int chunk = canny_pages_per_chunk(a.n_pages, ow, oh, pyr_bytes + last_bytes + gray_bytes);
+    const size_t tail_bytes = tail ? tail->scratch_per_page : 0;
+    const int chunk = canny_pages_per_chunk(a.n_pages, ow, oh, pyr_bytes + last_bytes + gray_bytes + tail_bytes);
     const size_t hist_bytes = channels > 1 ? (size_t)chunk * channels * 256 * sizeof(unsigned) : 0, ch_bytes = sizeof(int) * (size_t)chunk;
+    const size_t canny_bytes = canny_work_per_page(ow, oh) * (size_t)chunk + kCannyWorkSlack;
     WorkScope w;
-    int st = w.open(stream, (pyr_bytes + last_bytes + gray_bytes + canny_work_per_page(ow, oh)) * (size_t)chunk + kCannyWorkSlack,
-                    channels > 1 ? hist_bytes + ch_bytes : 0, std::max(hist_bytes + ch_bytes, canny_pinned_bytes(chunk)));
+    int st = w.open(stream, (pyr_bytes + last_bytes + gray_bytes + tail_bytes) * (size_t)chunk + r256(canny_bytes),
+                    std::max(channels > 1 ? hist_bytes + ch_bytes : 0, tail ? tail->small_per_page * (size_t)chunk : 0),
+                    std::max(std::max(hist_bytes + ch_bytes, canny_pinned_bytes(chunk)), tail ? tail->pinned_per_page * (size_t)chunk : 0));
     if (st != PRL_OK) return st;
     const hipStream_t hs = w.stream;
     uint8_t* pyr_work = w.scratch();
     uint8_t* last = pyr_work + pyr_bytes * (size_t)chunk;
     uint8_t* gray = last + last_bytes * (size_t)chunk;
     uint8_t* canny_work = gray + gray_bytes * (size_t)chunk;
+    uint8_t* tail_work = canny_work + r256(canny_bytes);
     const CannyCfg c{ow, oh, 25, 50};   // autoCrop.cpp:99-101
     for (int first = 0; first < a.n_pages; first += chunk) {
         const int n = std::min(chunk, a.n_pages - first);
@@ -484,8 +497,10 @@ int doc_batch(const PageArgs& a, int channels, int32_t* out_channel, void* strea
             int* h_ch = reinterpret_cast<int*>(w.pinned() + hist_bytes);
             PRL_HIP_CHECK(hipMemcpyAsync(h_hist, d_hist, (size_t)n * channels * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, hs));
             PRL_HIP_CHECK(hipStreamSynchronize(hs));
-            for (int i = 0; i < n; ++i)
-                out_channel[first + i] = h_ch[i] = most_informative_channel(h_hist + (size_t)i * channels * 256, channels, (double)ow * (double)oh);
+            for (int i = 0; i < n; ++i) {
+                h_ch[i] = most_informative_channel(h_hist + (size_t)i * channels * 256, channels, (double)ow * (double)oh);
+                if (out_channel) out_channel[first + i] = h_ch[i];
+            }
             PRL_HIP_CHECK(hipMemcpyAsync(d_ch, h_ch, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, hs));
             const PageSetOut gp = page_set_out(gray, gray_bytes, (size_t)ow);
             const dim3 grid((unsigned)((ow + 255) / 256), (unsigned)oh, (unsigned)n);
@@ -493,14 +508,86 @@ int doc_batch(const PageArgs& a, int channels, int32_t* out_channel, void* strea
             else hipLaunchKernelGGL(k_take_channel<4>, grid, dim3(256), 0, hs, cur, gp, ow, d_ch);
             PRL_HIP_CHECK(hipGetLastError());
             cur = as_source(gp);
-        } else {
+        } else if (out_channel) {
             for (int i = 0; i < n; ++i) out_channel[first + i] = 0;
         }
         // (canny_run synchronises the stream before it touches the pinned block again: the copy of the channels has left it)
-        st = canny_run(c, cur, dst_pages(a, first), n, canny_work, w.pinned<unsigned>(), hs);
+        const PageSetOut maps = tail ? page_set_out(tail_work, r256((size_t)ow * (size_t)oh), (size_t)ow) : dst_pages(a, first);
+        st = canny_run(c, cur, maps, n, canny_work, w.pinned<unsigned>(), hs);
         if (st != PRL_OK) return st;
+        if (tail && (st = tail->run(first, n, tail_work, w)) != PRL_OK) return st;
     }
     return PRL_OK;
+}
+
+// ---- prl::documentContour: the edge map, the quad search on the host (contour.h), one retry after a closing --------------------
+
+int contour_checks(const PageArgs& a, int channels, const float* quads, const int32_t* found, bool batch)
+{
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
+    if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
+    if ((st = pages_rows_ok(a, channels, 0, batch)) != PRL_OK) return st;
+    if (!quads || !found) return PRL_ERR_BAD_ARG;
+    return pages_sides_ok(a);
+}
+
+int contour_batch(const PageArgs& a, int channels, float* quads, int32_t* found, int32_t* out_try, void* stream)
+{
+    if (a.n_pages == 0) return PRL_OK;
+    int levels, ow, oh;
+    edges_geometry(a.width, a.height, &levels, &ow, &oh);
+    const int from_w = a.width >> levels, from_h = a.height >> levels;   // autoCrop.cpp:83: cols / 2^levels, not the pyramid's size
+    const size_t map_bytes = r256((size_t)ow * (size_t)oh);
+    DocTail tail;
+    tail.scratch_per_page = 3 * map_bytes;   // the map, then the closing's two planes
+    tail.small_per_page = sizeof(uint8_t*);  // the table of the pages the closing takes
+    tail.pinned_per_page = map_bytes + sizeof(uint8_t*);
+    std::vector<int32_t> corners, again;
+    tail.run = [&](int first, int n, uint8_t* maps, const WorkScope& w) -> int {
+        uint8_t* h_maps = w.pinned();
+        PRL_HIP_CHECK(hipMemcpyAsync(h_maps, maps, map_bytes * (size_t)n, hipMemcpyDeviceToHost, w.stream));
+        PRL_HIP_CHECK(hipStreamSynchronize(w.stream));
+        corners.assign((size_t)n * 8, 0);
+        auto search = [&](int i) {
+            CtPoint q[4];
+            const bool ok = ct_document_quad(h_maps + map_bytes * (size_t)i, (size_t)ow, ow, oh, q);
+            found[first + i] = ok ? 1 : 0;
+            for (int k = 0; ok && k < 4; ++k) {
+                corners[(size_t)i * 8 + 2 * k] = q[k].x;
+                corners[(size_t)i * 8 + 2 * k + 1] = q[k].y;
+            }
+        };
+        host_pool_for(n, search);
+        again.clear();
+        for (int i = 0; i < n; ++i) {
+            if (out_try) out_try[first + i] = found[first + i] ? 0 : 1;
+            if (!found[first + i]) again.push_back(i);
+        }
+        if (!again.empty()) {   // autoCrop.cpp:118-125, first round: CLOSE(2 x 2, iterations 2) on these pages only, in place
+            const int m = (int)again.size();
+            uint8_t** h_table = reinterpret_cast<uint8_t**>(h_maps + map_bytes * (size_t)n);
+            for (int k = 0; k < m; ++k) h_table[k] = maps + map_bytes * (size_t)again[k];
+            uint8_t** d_table = w.small<uint8_t*>();
+            PRL_HIP_CHECK(hipMemcpyAsync(d_table, h_table, sizeof(uint8_t*) * (size_t)m, hipMemcpyHostToDevice, w.stream));
+            const int st = gmorph_close_rect_table_run(2, 2, ow, oh, d_table, (size_t)ow, m, maps + map_bytes * (size_t)n, w.stream);
+            if (st != PRL_OK) return st;
+            for (int k = 0; k < m; ++k)
+                PRL_HIP_CHECK(hipMemcpyAsync(h_maps + map_bytes * (size_t)again[k], h_table[k], (size_t)ow * (size_t)oh, hipMemcpyDeviceToHost,
+                                             w.stream));
+            PRL_HIP_CHECK(hipStreamSynchronize(w.stream));
+            host_pool_for(m, [&](int k) { search(again[k]); });
+        }
+        for (int i = 0; i < n; ++i) {
+            float* out = quads + (size_t)(first + i) * 8;
+            if (!found[first + i] || !ct_finish(&corners[(size_t)i * 8], from_w, from_h, a.width, a.height, out)) {
+                found[first + i] = 0;
+                std::fill(out, out + 8, 0.0f);
+            }
+        }
+        return PRL_OK;
+    };
+    return doc_batch(a, channels, nullptr, stream, &tail);
 }
 
 }  // namespace
@@ -606,6 +693,86 @@ int prl_hip_document_edges_host(int channels, const uint8_t* src, size_t src_ste
     int levels, ow, oh;
     edges_geometry(width, height, &levels, &ow, &oh);
     return stage_host_pages(a, channels, 1, ow, oh, [&](const PageArgs& page, hipStream_t s) { return doc_batch(page, channels, out_channel, s); });
+}
+
+int prl_hip_find_contours(const uint8_t* map, size_t step, int width, int height, int32_t* points, int max_points, int32_t* contours,
+                          int max_contours, int* n_points, int* n_contours)
+{
+    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    if (!map || step < (size_t)width || !n_points || !n_contours || max_points < 0 || max_contours < 0 || (max_points && !points) ||
+        (max_contours && !contours))
+        return PRL_ERR_BAD_ARG;
+    std::vector<CtPoint> pts;
+    std::vector<CtContour> cs;
+    ct_find_contours(map, step, width, height, &pts, &cs);
+    *n_points = (int)pts.size();
+    *n_contours = (int)cs.size();
+    if ((int)pts.size() > max_points || (int)cs.size() > max_contours) return PRL_OK;   // the counts alone: call again with room
+    for (size_t i = 0; i < pts.size(); ++i) {
+        points[2 * i] = pts[i].x;
+        points[2 * i + 1] = pts[i].y;
+    }
+    for (size_t i = 0; i < cs.size(); ++i) {
+        contours[2 * i] = cs[i].count;
+        contours[2 * i + 1] = cs[i].hole;
+    }
+    return PRL_OK;
+}
+
+int prl_hip_approx_poly_closed(const int32_t* points, int n_points, double epsilon, int32_t* out_points, int* n_out)
+{
+    if (n_points < 0 || (n_points && (!points || !out_points)) || !n_out || !(epsilon >= 0)) return PRL_ERR_BAD_ARG;
+    std::vector<CtPoint> src((size_t)n_points), dst((size_t)n_points);
+    for (int i = 0; i < n_points; ++i) src[(size_t)i] = CtPoint{points[2 * i], points[2 * i + 1]};
+    *n_out = ct_approx_closed(src.data(), n_points, epsilon, dst.data());
+    for (int i = 0; i < *n_out; ++i) {
+        out_points[2 * i] = dst[(size_t)i].x;
+        out_points[2 * i + 1] = dst[(size_t)i].y;
+    }
+    return PRL_OK;
+}
+
+int prl_hip_document_quad(const uint8_t* map, size_t step, int width, int height, int32_t quad[8], int* found)
+{
+    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
+    if (!map || step < (size_t)width || !quad || !found || width > kStageMaxSide || height > kStageMaxSide) return PRL_ERR_BAD_ARG;
+    CtPoint q[4];
+    *found = ct_document_quad(map, step, width, height, q) ? 1 : 0;
+    for (int k = 0; k < 4; ++k) {
+        quad[2 * k] = *found ? q[k].x : 0;
+        quad[2 * k + 1] = *found ? q[k].y : 0;
+    }
+    return PRL_OK;
+}
+
+int prl_hip_document_quad_finish(const int32_t quad[8], int map_width, int map_height, int src_width, int src_height, float out[8])
+{
+    if (map_width <= 0 || map_height <= 0 || src_width <= 0 || src_height <= 0) return PRL_ERR_EMPTY;
+    if (!quad || !out) return PRL_ERR_BAD_ARG;
+    float r[8];
+    if (!ct_finish(quad, map_width, map_height, src_width, src_height, r)) return PRL_ERR_BAD_ARG;   // not strictly convex
+    std::copy(r, r + 8, out);
+    return PRL_OK;
+}
+
+int prl_hip_document_contour_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                          int height, float* quads, int32_t* found, int32_t* out_try, void* stream)
+{
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, nullptr, 0, 0};
+    const int st = contour_checks(a, channels, quads, found, true);
+    if (st != PRL_OK) return st;
+    return contour_batch(a, channels, quads, found, out_try, stream);
+}
+
+int prl_hip_document_contour_host(int channels, const uint8_t* src, size_t src_step, int width, int height, float quad[8], int32_t* found,
+                                  int32_t* out_try)
+{
+    uint8_t unused = 0;   // the staging helper brings a result down: one byte that nobody reads
+    const PageArgs a{1, src, 0, src_step, width, height, &unused, 0, 1};
+    const int st = contour_checks(a, channels, quad, found, false);
+    if (st != PRL_OK) return st;
+    return stage_host_pages(a, channels, 1, 1, 1,
+                            [&](const PageArgs& page, hipStream_t s) { return contour_batch(page, channels, quad, found, out_try, s); });
 }
 
 }  // extern "C"

@@ -1,10 +1,12 @@
 // gmorph.hip — flat-element grayscale morphology on 8-bit pages of 1..4 interleaved channels: cv::erode / cv::dilate /
-// cv::morphologyEx with cv::getStructuringElement(RECT | CROSS | ELLIPSE, Size(kw, kh)), one iteration, and on top of it
+// cv::morphologyEx with cv::getStructuringElement(RECT | CROSS | ELLIPSE, Size(kw, kh)), an anchor and iterations, and on top of it
 // prl::correctNUIL (src/correctNUIL.cpp:33-90): per channel, invert where the page's mean is below 128, then
 // 255 - blackhat(channel, ellipse(size, size)).
 //
-//   dst(y, x, c) = min / max over the element's set pixels (i, j) of src(y + i - kh/2, x + j - kw/2, c); taps outside the page
-//   are ignored (morphologyDefaultBorderValue); the element is NOT reflected between the two operators.
+//   dst(y, x, c) = min / max over the element's set pixels (i, j) of src(y + i - ay, x + j - ax, c), (ax, ay) the anchor (the
+//   centre (kw/2, kh/2) unless the caller names one); taps outside the page are ignored (morphologyDefaultBorderValue); the
+//   element is NOT reflected between the two operators.  n iterations of a full rectangle run once with the rectangle grown to
+//   1 + n (k - 1) a side and the anchor n times as far [upstream]; any other element runs n passes (gm_add).
 //
 // Row i of every element is one half-open span [j1, j2) of columns (gm_spans).  So an output is a max over at most kh
 // horizontal span maxima, and a span of w pixels is the max of two windows of 2^k <= w pixels that overlap.
@@ -36,6 +38,7 @@ namespace prl_hip {
 namespace {
 
 constexpr int kGmMaxK = 255;          // element sizes 1..255 (the spans travel as bytes in the kernel arguments)
+constexpr int kGmMaxIters = 16;        // cv::morphologyEx's `iterations`
 constexpr int kGmThreads = 256;
 constexpr int kGmItems = 4;           // output dwords per lane of k_gm_span
 constexpr int kGmLdsBytes = 64 * 1024;   // both level buffers of a workgroup: at least two workgroups per CU (160 KiB)
@@ -397,32 +400,61 @@ struct GmPlan {
     int planes = 0;   // scratch planes per page
 };
 
-// erode / dilate with the element; a rectangle as its two one-dimensional passes unless `literal`
-void gm_add(GmPlan* plan, int shape, int kw, int kh, int erode, bool literal)
+// erode / dilate with the element, `iters` times, anchor (ax, ay).  A full rectangle runs once, grown to 1 + iters (k - 1) a
+// side with the anchor iters times as far [upstream, morph.cpp], as its two one-dimensional passes unless `literal`; any other
+// element runs `iters` real passes.
+void gm_add(GmPlan* plan, int shape, int kw, int kh, int ax, int ay, int iters, int erode, bool literal)
 {
     std::vector<int> j1, j2;
     gm_spans(shape, kw, kh, &j1, &j2);
     bool rect = true;
     for (int i = 0; i < kh; ++i) rect = rect && j1[i] == 0 && j2[i] == kw;
-    if (rect && !literal && kw > 1 && kh > 1) {
-        plan->steps.push_back({gm_rect(kw, 1, kw / 2, 0), erode});
-        plan->steps.push_back({gm_rect(1, kh, 0, kh / 2), erode});
-    } else {
-        plan->steps.push_back({gm_elem(kw, kh, kw / 2, kh / 2, j1, j2), erode});
+    if (rect) {
+        kw = 1 + iters * (kw - 1);
+        kh = 1 + iters * (kh - 1);
+        ax *= iters;
+        ay *= iters;
+        if (!literal && kw > 1 && kh > 1) {
+            plan->steps.push_back({gm_rect(kw, 1, ax, 0), erode});
+            plan->steps.push_back({gm_rect(1, kh, 0, ay), erode});
+        } else {
+            plan->steps.push_back({gm_rect(kw, kh, ax, ay), erode});
+        }
+        return;
     }
+    for (int i = 0; i < iters; ++i) plan->steps.push_back({gm_elem(kw, kh, ax, ay, j1, j2), erode});
 }
 
-GmPlan gm_plan(int op, int shape, int kw, int kh, bool nuil, bool in_place, bool literal)
+struct GmOp {
+    int op, shape, kw, kh;
+    bool nuil;
+    int ax = -1, ay = -1;   // -1: the centre k / 2
+    int iters = 1;
+};
+
+// every row of the element is full: what gm_add grows over the iterations
+bool gm_is_rect(int shape, int kw, int kh)
+{
+    std::vector<int> j1, j2;
+    gm_spans(shape, kw, kh, &j1, &j2);
+    for (int i = 0; i < kh; ++i)
+        if (j1[i] != 0 || j2[i] != kw) return false;
+    return true;
+}
+
+GmPlan gm_plan(const GmOp& o, bool in_place, bool literal)
 {
     GmPlan plan;
-    plan.nuil = nuil;
+    plan.nuil = o.nuil;
+    const int op = o.op, ax = o.ax < 0 ? o.kw / 2 : o.ax, ay = o.ay < 0 ? o.kh / 2 : o.ay;
     const bool first_erodes = op == PRL_MORPH_ERODE || op == PRL_MORPH_OPEN || op == PRL_MORPH_TOPHAT;
-    gm_add(&plan, shape, kw, kh, first_erodes ? 1 : 0, literal);
-    if (op != PRL_MORPH_ERODE && op != PRL_MORPH_DILATE) gm_add(&plan, shape, kw, kh, first_erodes ? 0 : 1, literal);
+    gm_add(&plan, o.shape, o.kw, o.kh, ax, ay, o.iters, first_erodes ? 1 : 0, literal);
+    if (op != PRL_MORPH_ERODE && op != PRL_MORPH_DILATE) gm_add(&plan, o.shape, o.kw, o.kh, ax, ay, o.iters, first_erodes ? 0 : 1, literal);
     if (op == PRL_MORPH_TOPHAT) plan.ep = EP_TOPHAT;
-    if (op == PRL_MORPH_BLACKHAT) plan.ep = nuil ? EP_NUIL : EP_BLACKHAT;
+    if (op == PRL_MORPH_BLACKHAT) plan.ep = o.nuil ? EP_NUIL : EP_BLACKHAT;
     // a single pass must not write the pages whose neighbourhoods other workgroups still read: start from a copy
-    if (in_place && plan.steps.size() == 1 && (kw > 1 || kh > 1)) plan.steps.insert(plan.steps.begin(), {gm_rect(1, 1, 0, 0), 0});
+    if (in_place && plan.steps.size() == 1 && (plan.steps[0].el.kw > 1 || plan.steps[0].el.kh > 1))
+        plan.steps.insert(plan.steps.begin(), {gm_rect(1, 1, 0, 0), 0});
     plan.planes = (int)std::min<size_t>(2, plan.steps.size() - 1);
     return plan;
 }
@@ -468,8 +500,6 @@ bool gm_known_op(int op)
            op == PRL_MORPH_BLACKHAT;
 }
 
-struct GmOp { int op, shape, kw, kh; bool nuil; };
-
 // the checks every entry makes, in the documented order (no device is touched); batch: a *_batch_device entry
 int gm_checks(const PageArgs& a, int channels, const GmOp& o, bool batch)
 {
@@ -477,6 +507,9 @@ int gm_checks(const PageArgs& a, int channels, const GmOp& o, bool batch)
     if (st != PRL_OK) return st;
     if (!gm_known_op(o.op) || o.shape < PRL_SHAPE_RECT || o.shape > PRL_SHAPE_ELLIPSE || o.kw < 1 || o.kh < 1 || o.kw > kGmMaxK ||
         o.kh > kGmMaxK)
+        return PRL_ERR_BAD_ARG;
+    if (o.ax < -1 || o.ax >= o.kw || o.ay < -1 || o.ay >= o.kh || o.iters < 1 || o.iters > kGmMaxIters) return PRL_ERR_BAD_ARG;
+    if (o.iters > 1 && gm_is_rect(o.shape, o.kw, o.kh) && (1 + o.iters * (o.kw - 1) > kGmMaxK || 1 + o.iters * (o.kh - 1) > kGmMaxK))
         return PRL_ERR_BAD_ARG;
     if (channels < 1 || channels > 4) return PRL_ERR_BAD_CHANNELS;
     if ((st = pages_rows_ok(a, channels, channels, batch)) != PRL_OK) return st;
@@ -491,7 +524,7 @@ int gm_batch_device(const PageArgs& a, int channels, const GmOp& o, void* stream
     if (st != PRL_OK) return st;
     if (a.n_pages == 0) return PRL_OK;
     const bool literal = env_knobs().gmorph_literal;
-    const GmPlan plan = gm_plan(o.op, o.shape, o.kw, o.kh, o.nuil, pages_in_place(a, channels, channels), literal);
+    const GmPlan plan = gm_plan(o, pages_in_place(a, channels, channels), literal);
     const size_t page_bytes = (size_t)a.width * channels * (size_t)a.height;
     // pages per launch: grid.z, and at most 4 GiB of scratch (one page at least)
     const int chunk = stage_chunk(a.n_pages, page_bytes * plan.planes);
@@ -520,15 +553,26 @@ int gm_host(int channels, const GmOp& o, const uint8_t* src, size_t src_step, in
 int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
                          hipStream_t stream)
 {
-    const GmPlan plan = gm_plan(PRL_MORPH_OPEN, PRL_SHAPE_RECT, kw, kh, false, false, false);
+    const GmPlan plan = gm_plan(GmOp{PRL_MORPH_OPEN, PRL_SHAPE_RECT, kw, kh, false}, false, false);
     return gm_run(plan, width, height, 1, false, src, dst, n_pages, tmp, nullptr, stream);
 }
 
 int gmorph_dilate_rect_run(int k, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
                            hipStream_t stream)
 {
-    const GmPlan plan = gm_plan(PRL_MORPH_DILATE, PRL_SHAPE_RECT, k, k, false, false, false);
+    const GmPlan plan = gm_plan(GmOp{PRL_MORPH_DILATE, PRL_SHAPE_RECT, k, k, false}, false, false);
     return gm_run(plan, width, height, 1, false, src, dst, n_pages, tmp, nullptr, stream);
+}
+
+int gmorph_close_rect_table_run(int k, int iterations, int width, int height, uint8_t* const* d_table, size_t step, int n_pages,
+                                uint8_t* tmp, hipStream_t stream)
+{
+    const bool literal = env_knobs().gmorph_literal;
+    GmOp o{PRL_MORPH_CLOSE, PRL_SHAPE_RECT, k, k, false};
+    o.iters = iterations;
+    const GmPlan plan = gm_plan(o, true, literal);
+    const PageSetOut pages = page_table_out(d_table, step);
+    return gm_run(plan, width, height, 1, literal, as_source(pages), pages, n_pages, tmp, nullptr, stream);
 }
 
 }  // namespace prl_hip
@@ -549,6 +593,21 @@ int prl_hip_morphology_host(int channels, int op, int shape, int ksize_w, int ks
                             int height, uint8_t* dst, size_t dst_step)
 {
     return gm_host(channels, GmOp{op, shape, ksize_w, ksize_h, false}, src, src_step, width, height, dst, dst_step);
+}
+
+int prl_hip_morphology_ex_batch_device(int n_pages, int channels, int op, int shape, int ksize_w, int ksize_h, int anchor_x, int anchor_y,
+                                       int iterations, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
+                                       uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
+{
+    return gm_batch_device(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
+                           GmOp{op, shape, ksize_w, ksize_h, false, anchor_x, anchor_y, iterations}, stream);
+}
+
+int prl_hip_morphology_ex_host(int channels, int op, int shape, int ksize_w, int ksize_h, int anchor_x, int anchor_y, int iterations,
+                               const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
+{
+    return gm_host(channels, GmOp{op, shape, ksize_w, ksize_h, false, anchor_x, anchor_y, iterations}, src, src_step, width, height, dst,
+                   dst_step);
 }
 
 int prl_hip_correct_nuil_batch_device(int n_pages, int channels, int size, const uint8_t* d_src, size_t src_page_stride,

@@ -42,6 +42,13 @@ WorkPool& copy_pool()
     return *pool;
 }
 
+}  // namespace
+
+void host_pool_for(int n, const std::function<void(int)>& f) { copy_pool().parallel_for(n, f); }
+int host_pool_threads() { return copy_pool().threads(); }
+
+namespace {
+
 // pages [0, n) between the caller's strided pages and a packed buffer, in tasks of about a megabyte
 void copy_pages(int n, size_t row_bytes, int rows, const uint8_t* const* src, size_t src_step, uint8_t* dst_packed, bool to_packed,
                 uint8_t* const* dst_pages, size_t dst_step, int /*threads*/)

@@ -67,6 +67,7 @@ public:
 };
 typedef Point_<int> Point2i;
 typedef Point2i Point;
+typedef Point_<float> Point2f;
 
 template <typename _Tp> class Scalar_ {
 public:

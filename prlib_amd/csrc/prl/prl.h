@@ -21,6 +21,7 @@
 //   src/cleanBackgroundToWhite.h:40                        prl::cleanBackgroundToWhite
 //   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
 //   src/warp.h:49-73                                       prl::warpCrop
+//   src/border_detection/autoCrop.h:42-53                  prl::documentContour, prl::autoCrop
 //   src/resize.h:32                                        prl::resize
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
@@ -190,6 +191,18 @@ CV_EXPORTS void warpCrop(const cv::Mat& inputImage, cv::Mat& outputImage, const 
               const cv::Scalar& borderValue = cv::Scalar());
 CV_EXPORTS void warpCrop(cv::Mat& inputImage, cv::Mat& outputImage, const std::vector<cv::Point>& points, double ratio = -1.0,
               int borderMode = 0, const cv::Scalar& borderValue = cv::Scalar());
+
+// src/border_detection/autoCrop.h:42-53 - the page in a photograph as four corners, and the page itself (autoCrop.cpp:43-175; the
+// arithmetic is stated in prl_hip.h, "document contour").  documentContour: the edge map on the device (pyramid, most informative
+// channel, cv::Canny(25, 50)), the quad search on the host, one retry after a closing; true and the corners top left, top right,
+// bottom right, bottom left in source coordinates, or false and an empty vector.  cv::Point_<float> is cv::Point2f.  Positive
+// scaleX and scaleY (cv::resize, INTER_AREA) are cv::Exception StsNotImplemented; std::invalid_argument for an empty image;
+// StsUnsupportedFormat for a depth other than CV_8U or channels other than 1, 3, 4.  autoCrop: as the reference, a CV_8UC1 input
+// becomes BGR in the caller's Mat; the corners are truncated to int and handed to prl::warpCrop(in, out, points); false, and
+// outputImage untouched, when no quad is found; std::invalid_argument("autoCrop: Image for cropping is empty").
+CV_EXPORTS bool documentContour(cv::Mat& inputImage, const double scaleX, const double scaleY,
+                                std::vector<cv::Point_<float> >& resultContour);
+CV_EXPORTS bool autoCrop(cv::Mat& inputImage, cv::Mat& outputImage);
 
 // src/resize.h:32 (no defaults, as there) - resize.cpp:29-62 (pyr.hip; the arithmetic is stated in prl_hip.h).  scaleX > 0 and
 // scaleY > 0: cv::resize(INTER_AREA) to cols * scaleX x rows * scaleY, an exact replication through OpenCV's float64 index tables.

@@ -501,6 +501,56 @@ void prl::warpCrop(cv::Mat& inputImage, cv::Mat& outputImage, const std::vector<
              points[3].y, ratio, borderMode, borderValue);
 }
 
+// autoCrop.cpp:43-131.  The reference reads the image without a check of its own: an empty one fails in cv::meanStdDev / cv::split
+// [upstream]; here it is the C layer's PRL_ERR_EMPTY, std::invalid_argument.
+bool prl::documentContour(cv::Mat& inputImage, const double scaleX, const double scaleY, std::vector<cv::Point_<float> >& resultContour)
+{
+    if (scaleX > 0 && scaleY > 0)
+        PRL_FAIL_CV(cv::Error::StsNotImplemented, "prl::documentContour: positive scaleX / scaleY (cv::resize, INTER_AREA) are not provided");
+    if (inputImage.empty()) raise(PRL_ERR_EMPTY);
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::documentContour: 8-bit images only");
+    float quad[8];
+    int32_t found = 0;
+    const int st = prl_hip_document_contour_host(inputImage.channels(), inputImage.data, inputImage.step, inputImage.cols, inputImage.rows,
+                                                 quad, &found, nullptr);
+    if (st != PRL_OK) raise(st);
+    if (!found) {
+        resultContour.clear();   // :116
+        return false;
+    }
+    // findDocumentContour appends its four corners to what the caller's vector holds (autoCropUtils.cpp:248-256); scaleContour
+    // and cropVerticesOrdering then want exactly four, so anything but an empty vector throws there (:278-281)
+    if (!resultContour.empty()) throw std::invalid_argument("Points number in input contour isn't equal 4");
+    for (int i = 0; i < 4; ++i) resultContour.push_back(cv::Point_<float>(quad[2 * i], quad[2 * i + 1]));
+    return true;
+}
+
+// autoCrop.cpp:133-175
+bool prl::autoCrop(cv::Mat& inputImage, cv::Mat& outputImage)
+{
+    if (inputImage.empty()) throw std::invalid_argument("autoCrop: Image for cropping is empty");
+    if (inputImage.type() == CV_8UC1) {   // cv::cvtColor(inputImage, inputImage, cv::COLOR_GRAY2BGR): the caller's Mat becomes BGR
+#ifdef PRL_HAVE_OPENCV
+        cv::cvtColor(inputImage, inputImage, cv::COLOR_GRAY2BGR);
+#else
+        cv::Mat bgr(inputImage.rows, inputImage.cols, CV_8UC3);
+        for (int y = 0; y < inputImage.rows; ++y) {
+            const unsigned char* s = inputImage.ptr(y);
+            unsigned char* d = bgr.ptr(y);
+            for (int x = 0; x < inputImage.cols; ++x) d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = s[x];
+        }
+        inputImage = bgr;
+#endif
+    }
+    std::vector<cv::Point_<float> > resultContour;
+    if (!documentContour(inputImage, -1, -1, resultContour)) return false;
+    std::vector<cv::Point> temp;
+    temp.reserve(resultContour.size());
+    for (const auto& point : resultContour) temp.push_back(cv::Point((int)point.x, (int)point.y));   // :164-169: truncated
+    warpCrop(inputImage, outputImage, temp);
+    return true;
+}
+
 void prl::resize(const cv::Mat& src, cv::Mat& dst, int scaleX, int scaleY, int maxSize)
 {
     const bool by_scale = scaleX > 0 && scaleY > 0;

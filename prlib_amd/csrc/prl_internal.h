@@ -6,6 +6,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <deque>
+#include <functional>
 #include <map>
 #include <memory>
 #include <condition_variable>
@@ -478,6 +479,16 @@ int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& s
 // DILATE with a k x k rectangle (k odd, 3..255), anchor at the centre: the same conditions and `tmp` (binarizeMokji, mokji.hip)
 int gmorph_dilate_rect_run(int k, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
                            hipStream_t stream);
+// CLOSE with a k x k rectangle, default anchor, `iterations` times, IN PLACE on the 1-channel pages a DEVICE table of page
+// pointers names (rows `step` bytes apart): the border detector's retry on the pages without a quad (canny.hip).  `tmp`:
+// 2 * n_pages * width * height bytes; enqueues only (caller holds ctx->mu)
+int gmorph_close_rect_table_run(int k, int iterations, int width, int height, uint8_t* const* d_table, size_t step, int n_pages,
+                                uint8_t* tmp, hipStream_t stream);
+
+// ---- the host thread pool (host_batch.hip): the page copies of the host-list entries and the per-page host work of the stage
+// entries (the quad search of prl::documentContour) share it; parallel_for(n, f) as prl/work_pool.h states ----------
+void host_pool_for(int n, const std::function<void(int)>& f);
+int host_pool_threads();
 
 // ---- cv::pyrDown (pyr.hip): `levels` >= 1 pyramid levels of n pages of 1..4 channels into `dst` (pages of the last level's size);
 // `work`: n * pyr_work_per_page bytes for the levels between; enqueues only (caller holds ctx->mu) ----------

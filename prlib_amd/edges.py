@@ -5,6 +5,10 @@ Pages are what prlib_amd._pages takes: a numpy H x W [x C] uint8 image goes thro
 [N,] H x W [x C] is enqueued on the current stream.  cv::Canny and the two stages on their own take gray pages only (a
 3-dimensional tensor is N x H x W).  document_edges_geometry, pyr_down_size and resize_pyramid_levels are host code and need no
 device.
+
+The border detector on top of the edge map ("document contour" in the header): find_contours, approx_poly_closed, document_quad
+and document_quad_finish are the host search piece by piece (numpy maps, no device); document_contour is prl::documentContour on
+device pages or one host image, auto_crop is prl::autoCrop: the contour, its corners truncated to int, prl::warpCrop.
 """
 from __future__ import annotations
 
@@ -144,3 +148,92 @@ def resize(pages, scaleX: int, scaleY: int, maxSize: int, out=None):
         return _resized(pages, _pages.same, lambda w, h: (w, h), lambda c, *a: L.prl_hip_resize_replicate_host(c, 1, 1, *a),
                         lambda n, c, *a: L.prl_hip_resize_replicate_batch_device(n, c, 1, 1, *a), out)
     return pyr_down(pages, levels, out)
+
+
+def find_contours(edge_map):
+    """cv::findContours(map, RETR_CCOMP, CHAIN_APPROX_SIMPLE) on an H x W uint8 numpy map -> [(K x 2 int32 points, is_hole)] in
+    OpenCV's order.  Host code."""
+    m = _pages.host_image(edge_map, gray_only=True)
+    h, w = m.shape[:2]
+    L = _capi.lib()
+    npts, ncs = C.c_int(0), C.c_int(0)
+    _capi.check(L.prl_hip_find_contours(m.ctypes.data, m.strides[0], w, h, None, 0, None, 0, C.byref(npts), C.byref(ncs)))
+    pts = np.zeros((max(npts.value, 1), 2), np.int32)
+    cs = np.zeros((max(ncs.value, 1), 2), np.int32)
+    _capi.check(L.prl_hip_find_contours(m.ctypes.data, m.strides[0], w, h, pts.ctypes.data, npts.value, cs.ctypes.data, ncs.value,
+                                        C.byref(npts), C.byref(ncs)))
+    out, at = [], 0
+    for k in range(ncs.value):
+        out.append((pts[at:at + cs[k, 0]].copy(), bool(cs[k, 1])))
+        at += int(cs[k, 0])
+    return out
+
+
+def approx_poly_closed(points, epsilon: float):
+    """cv::approxPolyDP(points, epsilon, closed=True) on integer points -> K x 2 int32.  Host code."""
+    p = np.ascontiguousarray(np.asarray(points, dtype=np.int32).reshape(-1, 2))
+    out = np.zeros((max(len(p), 1), 2), np.int32)
+    n = C.c_int(0)
+    _capi.check(_capi.lib().prl_hip_approx_poly_closed(p.ctypes.data, len(p), float(epsilon), out.ctypes.data, C.byref(n)))
+    return out[:n.value].copy()
+
+
+def document_quad(edge_map):
+    """findDocumentContour on an H x W uint8 numpy map: 4 x 2 int32 corners in the polygon's own order, or None.  Host code."""
+    m = _pages.host_image(edge_map, gray_only=True)
+    h, w = m.shape[:2]
+    quad, found = np.zeros(8, np.int32), C.c_int(0)
+    _capi.check(_capi.lib().prl_hip_document_quad(m.ctypes.data, m.strides[0], w, h, quad.ctypes.data, C.byref(found)))
+    return quad.reshape(4, 2) if found.value else None
+
+
+def document_quad_finish(quad, map_size, src_size):
+    """scaleContour from map_size = (w, h) to src_size, then cropVerticesOrdering -> 4 x 2 float32.  Host code."""
+    q = np.ascontiguousarray(np.asarray(quad, dtype=np.int32).reshape(8))
+    out = np.zeros(8, np.float32)
+    _capi.check(_capi.lib().prl_hip_document_quad_finish(q.ctypes.data, int(map_size[0]), int(map_size[1]), int(src_size[0]),
+                                                         int(src_size[1]), out.ctypes.data))
+    return out.reshape(4, 2)
+
+
+def document_contour(pages):
+    """prl::documentContour(page, -1, -1, contour) per page -> (quads N x 4 x 2 float32, found N bool, tries N int32); for one
+    page (a numpy image or a tensor without a page axis) the three without the N."""
+    L = _capi.lib()
+    if isinstance(pages, np.ndarray):
+        img = _pages.host_image(pages)
+        h, w, c = img.shape
+        quads, found, tries = np.zeros((1, 4, 2), np.float32), np.zeros(1, np.int32), np.zeros(1, np.int32)
+        _capi.check(L.prl_hip_document_contour_host(c, img.ctypes.data, img.strides[0], w, h, quads.ctypes.data, found.ctypes.data,
+                                                    tries.ctypes.data))
+        return quads[0], bool(found[0]), int(tries[0])
+    t4, _chan, batch = _pages.pages4(pages)
+    n, h, w, c = t4.shape
+    quads, found, tries = np.zeros((max(n, 1), 4, 2), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    _capi.check(L.prl_hip_document_contour_batch_device(n, c, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h, quads.ctypes.data,
+                                                        found.ctypes.data, tries.ctypes.data, _capi.stream_on(pages)))
+    if not batch:
+        return quads[0], bool(found[0]), int(tries[0])
+    return quads[:n], found[:n].astype(bool), tries[:n]
+
+
+def auto_crop(pages, return_contour: bool = False):
+    """prl::autoCrop per page of an N x H x W [x C] tensor -> list of tensors, None for a page without a quad [, the
+    document_contour result].  The corners are truncated to int as the reference does; the destinations are sized with
+    warp_crop_size."""
+    from . import warp
+
+    t4, chan, batch = _pages.pages4(pages)
+    if not batch:
+        raise TypeError("expected pages N x H x W [x C]")
+    quads, found, tries = document_contour(pages)
+    out = [None] * t4.shape[0]
+    idx = [i for i in range(t4.shape[0]) if found[i]]
+    if idx:
+        import torch
+
+        q = quads[idx].astype(np.int32).reshape(-1, 8)   # (int)float: towards zero
+        src = pages if len(idx) == t4.shape[0] else pages[torch.as_tensor(idx, device=pages.device)]
+        for i, crop in zip(idx, warp.warp_crop(src, q)):
+            out[i] = crop
+    return (out, (quads, found, tries)) if return_contour else out
