@@ -1026,6 +1026,111 @@ int prl_hip_document_contour_batch_device(int n_pages, int channels, const uint8
 int prl_hip_document_contour_host(int channels, const uint8_t* src, size_t src_step, int width, int height, float quad[8], int32_t* found,
                                   int32_t* out_try);
 
+/* ---- Hough lines (cv::HoughLines; prl::findHoughLineContour: houghLine.cpp:16-256, imageLibCommon.cpp:821-833, 929-941,
+ *      autoCropUtils.cpp:350-366) ------------------------------------------------------------------------------------------------- */
+
+/*
+ * prl::findHoughLineContour is the reference's second border detector: where a page's outline is broken, contour following fails
+ * and voting lines succeed.  Edge map, votes and peaks run on the device; the line filter and the quad search run on the host, per
+ * page, on at most a few hundred lines.  The arithmetic below is restated in tests/houghline_ref.py; what is marked [upstream] is
+ * OpenCV's (hough.cpp HoughLinesStandard, canny.cpp, shapedescr.cpp, convhull.cpp of 3.4 / 4.x).  Parity with an installed OpenCV is
+ * not pinned.
+ *
+ * cv::HoughLines(map, lines, rho = 1, theta = (float)(CV_PI / 180), threshold), the standard transform [upstream], on an 8UC1 map of
+ * W x H pixels:
+ *     numangle = cvRound(CV_PI / theta) = 180: the rule of 3.4 and of 4.x up to the release that changed it.  Later 4.x releases
+ *         take cvFloor(CV_PI / theta) + 1 = 181 rows (an extra angle just below pi); that rule is NOT the one taken here.
+ *     numrho = cvRound(((W + H) * 2 + 1) / rho) = 2 (W + H) + 1.
+ *     the table, on the host with libm: float ang = 0; for n = 0..179: tabSin[n] = (float)(sin((double)ang) * 1.f), tabCos[n] likewise,
+ *         ang += theta in float32.  The device never evaluates sin or cos.
+ *     every non-zero pixel (x = column, y = row) votes once per n: r = cvRound(x * tabCos[n] + y * tabSin[n]) + (numrho - 1) / 2,
+ *         two float32 products and one float32 sum, each rounded on its own (no contraction), the sum rounded to the nearest integer,
+ *         ties to even; cell (n + 1, r + 1) of an accumulator of (numangle + 2) x (numrho + 2) int32 is incremented.  The accumulator
+ *         is an integer histogram: the order of the votes does not matter.
+ *         Denormals cannot matter: the table's only zero is tabSin[0]; its smallest other magnitude is |tabCos[90]| = 1.1165949e-06
+ *         (the float32 angle after 90 additions misses pi / 2 by that much), so every non-zero product, x and y being integers >= 1,
+ *         is at least 1.1e-06, far above the smallest normal float32 (1.2e-38), and the sum of two such products is zero or at
+ *         least one unit in the last place of the smaller one, 1.3e-13: normal as well.
+ *     cell (n, r), 0 <= n < 180, 0 <= r < numrho, with count a, is a peak iff a > threshold and a > left and a >= right and a > up
+ *         and a >= down: left / right are r -+ 1, up / down are n -+ 1; the frame cells (row 0, row 181, column 0, column numrho + 1)
+ *         are zero.
+ *     the peaks are ordered by count, descending, then by cell index (n + 1) * (numrho + 2) + r + 1, ascending.
+ *     a peak leaves as rho = (r - (numrho - 1) * 0.5f) * 1.f, theta = n * theta, both float32.
+ * Other rho / theta steps and the multi-scale variant are not offered.
+ *
+ * The edge map of prl::findHoughLineContour (houghLine.cpp:198-218) on a page of 1, 3 or 4 channels: cv::medianBlur(3) three times,
+ * cv::medianBlur(5) three times (prl_hip_median_batch_device's arithmetic, per channel), then cv::Canny(25, 50), apertureSize 3, L1
+ * magnitude, as stated under "pyramid, edge map, resize", with one rule more for colour pages [upstream]: per pixel, dx, dy and the
+ * magnitude |dx| + |dy| are those of the channel whose magnitude is largest, the first of equals (a fourth channel takes part as
+ * any other).  Non-maximum suppression, the thresholds and the linking then see one gradient per pixel.  Only these entries reach
+ * the colour rule: prl_hip_canny_* keep refusing colour pages.  The reference's three cv::imwrite("after_*.jpg") calls are debugging
+ * leftovers: no file is written here.
+ *
+ * The line filter and the quad search (houghLine.cpp:16-175, 231-255) on the lines in cv::HoughLines' order:
+ *     fewer than four lines: no quad (before the filter).
+ *     fromVec2f(rho, theta): a = cosf(theta), b = sinf(theta) (std::cos / std::sin of a float are the float overloads) widened to
+ *         float64; x0 = a * rho, y0 = b * rho; the line's two ends are (cvRound(x0 - 1000 b), cvRound(y0 + 1000 a)) and
+ *         (cvRound(x0 + 1000 b), cvRound(y0 - 1000 a)), stored as float32: integers.
+ *     distanceToLine(start, end, p) takes the ends as integer points: |(px - sx)(ey - sy) - (py - sy)(ex - sx)| as an int, widened,
+ *         over hypot(ex - sx, ey - sy).
+ *     deleteSimilarLines(lines, minDist = 5, step = 5, maxLines = 20): while more than 20 lines remain, one round: in order, every
+ *         line not yet dropped is kept and drops every later line j whose distance is < minDist, the distance of two lines being the
+ *         smallest of the four end-to-line distances.  A round that keeps fewer than four lines ends the filter: the round's INPUT is
+ *         cut to its first 20 lines and kept.  Else the kept lines are the next round's input and minDist grows by 5.
+ *     intersection(o1, p1, o2, p2) (autoCropUtils.cpp:350-366) in float32: x = o2 - o1, d1 = p1 - o1, d2 = p2 - o2,
+ *         cross = d1.x * d2.y - d1.y * d2.x; |cross| <= 1e-7 (as float64): none.  t1 = (x.x * d2.y - x.y * d2.x) / cross, a float32
+ *         quotient widened to float64; the point is o1 + (float)(d1 * t1), the product in float64, the sum in float32.
+ *     findMaxValidContour: for every ordered choice (i, j, k, m) of four different lines, the corners are intersection(j, i),
+ *         intersection(k, j), intersection(m, k), intersection(i, m), the first line's ends given first; a choice with a missing
+ *         intersection is skipped, as is one with a corner outside 0 <= x <= width, 0 <= y <= height (the reference's flag for
+ *         "outside" is named validCoord, and the comparison is strict: a corner ON x == width is kept).  The choice replaces the kept
+ *         one iff cv::isContourConvex [upstream: every turn dy * dx0 > dx * dy0 of one strict sign, in float32, a zero turn fails] and
+ *         IsQuadrangularConvex (cv::convexHull of the four points has four vertices) hold and cv::contourArea [upstream: float64 sum
+ *         of prev.x * y - prev.y * x, halved, absolute] is > the kept area, which starts at 0: of equal areas the first choice wins.
+ *         The hull test is decided here as "each corner lies strictly outside the triangle of the other three", on float64 cross
+ *         products of the float32 corners; after isContourConvex has passed it can differ from OpenCV's float32 scan only where a
+ *         turn's sign depends on the last bit of a float32 product.
+ *     the four corners leave truncated towards zero, static_cast<int>, in the choice's order; the C++ layer APPENDS them to the
+ *         caller's vector as the reference does.
+ * splitPage (a stub in the reference), a chain stage and host-list entries are not offered.
+ *
+ * Every entry checks in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_CHANNELS (the
+ * edge and contour entries: not 1, 3 or 4); PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row bytes, a side above 32768,
+ * threshold < 0, max_lines < 0, an accumulator page stride below the accumulator's bytes or not a multiple of 4, source and
+ * destination of the edge map sharing a byte).
+ */
+
+/* numangle (180) and numrho of a width x height map; host code, no device needed */
+int prl_hip_hough_lines_geometry(int width, int height, int* numangle, int* numrho);
+/* The voting stage alone: page i's framed accumulator, (numangle + 2) x (numrho + 2) int32 in row-major order, at
+ * d_accum + i * accum_page_stride bytes (device memory, every cell written).  Enqueues only. */
+int prl_hip_hough_accumulator_batch_device(int n_pages, const uint8_t* d_map, size_t page_stride, size_t step, int width, int height,
+                                           int32_t* d_accum, size_t accum_page_stride, void* stream);
+/* cv::HoughLines per page of a batch of 8UC1 device maps.  lines (host): page i's lines as (rho, theta) pairs from
+ * lines + 2 * max_lines * i, in OpenCV's order; n_lines (host, n_pages entries) always receives the number found, which may exceed
+ * max_lines: then the first max_lines of the order were written and the caller sees that it has to call again with room (nothing
+ * is clipped silently; max_lines = 0 with lines = NULL asks for the counts alone).  Per chunk of pages the counts and the peak
+ * lists come down once and are sorted on the host.  Waits for the stream. */
+int prl_hip_hough_lines_batch_device(int n_pages, const uint8_t* d_map, size_t page_stride, size_t step, int width, int height, int threshold,
+                                     float* lines, int max_lines, int32_t* n_lines, void* stream);
+int prl_hip_hough_lines_host(const uint8_t* map, size_t step, int width, int height, int threshold, float* lines, int max_lines,
+                             int32_t* n_lines);
+/* the edge map above as 0 / 255 bytes, one 8UC1 map of the page's size per page.  Waits for the stream. */
+int prl_hip_hough_edges_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                     int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_hough_edges_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+/* The line filter and the quad search on n_lines (rho, theta) pairs in cv::HoughLines' order, for a map of width x height: *found = 1
+ * and the four corners (x, y) in quad, or *found = 0 and zeros.  Host code, no device needed. */
+int prl_hip_hough_line_quad(const float* lines, int n_lines, int width, int height, int32_t quad[8], int* found);
+/* prl::findHoughLineContour per page of 1, 3 or 4 channels in device memory: found (host, 0 / 1 per page), quads (host, 8 ints per
+ * page: the four corners, zeros without a quad), out_lines (host or NULL): the lines cv::HoughLines(threshold 50) found on the page.
+ * Per chunk of pages: the edge maps, the votes and the peaks on the device, ONE read-back of the line lists, the filter and the search
+ * per page on the library's host thread pool.  Waits for the stream. */
+int prl_hip_hough_line_contour_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                            int width, int height, int32_t* quads, int32_t* found, int32_t* out_lines, void* stream);
+int prl_hip_hough_line_contour_host(int channels, const uint8_t* src, size_t src_step, int width, int height, int32_t quad[8], int32_t* found,
+                                    int32_t* out_lines);
+
 #ifdef __cplusplus
 }
 #endif

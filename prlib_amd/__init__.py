@@ -18,6 +18,7 @@ from .warp import perspective_transform, warp_crop, warp_crop_host, warp_crop_si
 from .edges import (canny, canny_classes, document_edges, document_edges_geometry, edge_link, pyr_down, pyr_down_size, resize,  # noqa: F401
                     resize_pyramid_levels, approx_poly_closed, auto_crop, document_contour, document_quad, document_quad_finish,
                     find_contours)
+from .houghline import hough_accumulator, hough_edges, hough_line_contour, hough_line_quad, hough_lines, hough_lines_geometry  # noqa: F401
 from .chain import bitwise_not, cvtColorBGR2GRAY, cvtColorGRAY2BGR, process_pages, process_pages_host  # noqa: F401
 from .binarizations import (  # noqa: F401
     FENG, NICK, NIBLACK, SAUVOLA, WOLFJOLION, binarize, binarizeFeng, binarizeNICK, binarizeNiblack,
@@ -28,6 +29,6 @@ from .binarizations import (  # noqa: F401
 __all__ = [
     "binarize", "binarizeSauvola", "binarizeNiblack", "binarizeWolfJolion", "binarizeNICK", "binarizeFeng", "binarizeByLocalVariances", "binarizeByLocalVariancesWithoutFilters",
     "adaptiveThreshold", "binarizeNativeAdaptive", "binarizeAT", "binarizeAGT", "binarizePureAdaptiveGaussian",
-    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "morphology_ex", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize", "resize_pyramid_levels", "find_contours", "approx_poly_closed", "document_quad", "document_quad_finish", "document_contour", "auto_crop", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
+    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "morphology_ex", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize", "resize_pyramid_levels", "find_contours", "approx_poly_closed", "document_quad", "document_quad_finish", "document_contour", "auto_crop", "hough_lines_geometry", "hough_accumulator", "hough_lines", "hough_edges", "hough_line_quad", "hough_line_contour", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
     "SAUVOLA", "NIBLACK", "WOLFJOLION", "NICK", "FENG",
 ]

@@ -75,6 +75,9 @@ EXPORTED_SYMBOLS = [
     "prl_hip_resize_pyramid_levels", "prl_hip_resize_replicate_batch_device", "prl_hip_resize_replicate_host",
     "prl_hip_find_contours", "prl_hip_approx_poly_closed", "prl_hip_document_quad", "prl_hip_document_quad_finish",
     "prl_hip_document_contour_batch_device", "prl_hip_document_contour_host",
+    "prl_hip_hough_lines_geometry", "prl_hip_hough_accumulator_batch_device", "prl_hip_hough_lines_batch_device", "prl_hip_hough_lines_host",
+    "prl_hip_hough_edges_batch_device", "prl_hip_hough_edges_host", "prl_hip_hough_line_quad",
+    "prl_hip_hough_line_contour_batch_device", "prl_hip_hough_line_contour_host",
 ]
 
 
@@ -261,6 +264,15 @@ def lib() -> C.CDLL:
         L.prl_hip_document_quad_finish.argtypes = [vp, i, i, i, i, vp]
         L.prl_hip_document_contour_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, vp, vp, vp]
         L.prl_hip_document_contour_host.argtypes = [i, vp, sz, i, i, vp, vp, vp]
+        L.prl_hip_hough_lines_geometry.argtypes = [i, i, P(C.c_int), P(C.c_int)]
+        L.prl_hip_hough_accumulator_batch_device.argtypes = [i, vp, sz, sz, i, i, vp, sz, vp]
+        L.prl_hip_hough_lines_batch_device.argtypes = [i, vp, sz, sz, i, i, i, vp, i, vp, vp]
+        L.prl_hip_hough_lines_host.argtypes = [vp, sz, i, i, i, vp, i, vp]
+        L.prl_hip_hough_edges_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_hough_edges_host.argtypes = [i, vp, sz, i, i, vp, sz]
+        L.prl_hip_hough_line_quad.argtypes = [vp, i, i, i, vp, P(C.c_int)]
+        L.prl_hip_hough_line_contour_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, vp, vp, vp]
+        L.prl_hip_hough_line_contour_host.argtypes = [i, vp, sz, i, i, vp, vp, vp]
         _lib = L
     return _lib
 

@@ -2,7 +2,10 @@
 // (src/border_detection/autoCrop.cpp:67-101): pyramid, most informative channel, edge map.  The arithmetic is stated in
 // include/prl_hip.h ("pyramid, edge map, resize") and restated in tests/edges_ref.py; all of it is integer but the channel choice.
 //
-//   k_canny_classes<BITS>  Sobel, |dx| + |dy|, non-maximum suppression and the two thresholds.  A workgroup owns kCnTW columns and
+// The edge map and the contour entry of prl::findHoughLineContour (houghLine.cpp:177-256) are at the end: the only callers of the
+// colour instantiations (CH = 3, 4) of the classes kernel; the public cv::Canny entries keep refusing colour pages.
+//
+//   k_canny_classes<BITS, CH>  Sobel, |dx| + |dy|, non-maximum suppression and the two thresholds.  A workgroup owns kCnTW columns and
 //                          walks down kCnRows rows: per source row it stages the clamped pixels (BORDER_REPLICATE) in an LDS ring of
 //                          three rows, forms the magnitudes of the row above for its columns and one halo column each side (zero
 //                          outside the page) in a second ring of three rows, and decides the row above that.  BITS: a wavefront's
@@ -22,6 +25,7 @@
 #include <vector>
 
 #include "contour.h"
+#include "houghline.h"
 #include "prl_internal.h"
 
 namespace prl_hip {
@@ -42,11 +46,11 @@ struct CannyCfg {
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 // grid = (ceil(W / kCnTW), ceil(H / kCnRows), pages)
-template <bool BITS>
+template <bool BITS, int CH>
 __global__ __launch_bounds__(kCnTW) void k_canny_classes(CannyCfg c, PageSet src, PageSetOut dst, u64* __restrict__ strong,
                                                          u64* __restrict__ cand, size_t plane_words, int wpr)
 {
-    __shared__ uint8_t px[3][kCnTW + 4];          // pixel row j in slot (j + 3) % 3: columns x0 - 2 .. x0 + kCnTW + 1, clamped
+    __shared__ uint8_t px[3][(kCnTW + 4) * CH];   // pixel row j in slot (j + 3) % 3: columns x0 - 2 .. x0 + kCnTW + 1, clamped
     __shared__ unsigned short mg[3][kCnTW + 2];   // magnitudes of row r in slot (r + 3) % 3: columns x0 - 1 .. x0 + kCnTW
     const int t = threadIdx.x, x0 = blockIdx.x * kCnTW, x = x0 + t, page = blockIdx.z;
     const uint8_t* sp = src.page(page);
@@ -56,7 +60,7 @@ __global__ __launch_bounds__(kCnTW) void k_canny_classes(CannyCfg c, PageSet src
         {
             const uint8_t* prow = sp + (size_t)clampi(j, 0, c.H - 1) * src.step;
             uint8_t* pj = px[(j + 3) % 3];
-            for (int i = t; i < kCnTW + 4; i += kCnTW) pj[i] = prow[clampi(x0 - 2 + i, 0, c.W - 1)];
+            for (int i = t; i < (kCnTW + 4) * CH; i += kCnTW) pj[i] = prow[clampi(x0 - 2 + i / CH, 0, c.W - 1) * CH + i % CH];
         }
         __syncthreads();
         dx_prev = dx_cur;
@@ -68,12 +72,24 @@ __global__ __launch_bounds__(kCnTW) void k_canny_classes(CannyCfg c, PageSet src
             const uint8_t* pc = px[(r + 4) % 3];
             unsigned short* mr = mg[(r + 3) % 3];
             const bool row_in = r >= 0 && r < c.H;
-            // magnitude column i is page column x0 - 1 + i and pixel column i + 1 of the ring
+            // magnitude column i is page column x0 - 1 + i and pixel column i + 1 of the ring.  Colour pages (CH > 1, the edge map
+            // of prl::findHoughLineContour alone): the gradient of the channel of largest magnitude, the first of equals
             auto grad = [&](int i, int* gx, int* gy) {
-                *gx = ((int)pa[i + 2] + 2 * (int)pb[i + 2] + (int)pc[i + 2]) - ((int)pa[i] + 2 * (int)pb[i] + (int)pc[i]);
-                *gy = ((int)pc[i] + 2 * (int)pc[i + 1] + (int)pc[i + 2]) - ((int)pa[i] + 2 * (int)pa[i + 1] + (int)pa[i + 2]);
+                int best = -1;
+#pragma unroll
+                for (int ch = 0; ch < CH; ++ch) {
+                    const int l = i * CH + ch, m = l + CH, r2 = l + 2 * CH;
+                    const int dx = ((int)pa[r2] + 2 * (int)pb[r2] + (int)pc[r2]) - ((int)pa[l] + 2 * (int)pb[l] + (int)pc[l]);
+                    const int dy = ((int)pc[l] + 2 * (int)pc[m] + (int)pc[r2]) - ((int)pa[l] + 2 * (int)pa[m] + (int)pa[r2]);
+                    const int mag = abs(dx) + abs(dy);
+                    if (mag > best) {
+                        best = mag;
+                        *gx = dx;
+                        *gy = dy;
+                    }
+                }
                 const int xc = x0 - 1 + i;
-                mr[i] = (unsigned short)((row_in && xc >= 0 && xc < c.W) ? abs(*gx) + abs(*gy) : 0);
+                mr[i] = (unsigned short)((row_in && xc >= 0 && xc < c.W) ? best : 0);
             };
             grad(t + 1, &dx_cur, &dy_cur);
             if (t < 2) {
@@ -306,11 +322,13 @@ LinkWork link_work(const LinkGeom& g, int n, uint8_t* work)
 }
 
 int classes_launch(const CannyCfg& c, bool bits, const PageSet& s, const PageSetOut& d, int n, const LinkGeom& g, const LinkWork& w,
-                   hipStream_t hs)
+                   hipStream_t hs, int channels = 1)
 {
     const dim3 grid((unsigned)((c.W + kCnTW - 1) / kCnTW), (unsigned)((c.H + kCnRows - 1) / kCnRows), (unsigned)n);
-    if (bits) hipLaunchKernelGGL(k_canny_classes<true>, grid, dim3(kCnTW), 0, hs, c, s, d, w.S, w.C, g.plane_words, g.wpr);
-    else hipLaunchKernelGGL(k_canny_classes<false>, grid, dim3(kCnTW), 0, hs, c, s, d, (u64*)nullptr, (u64*)nullptr, (size_t)0, 0);
+    if (bits && channels == 3) hipLaunchKernelGGL((k_canny_classes<true, 3>), grid, dim3(kCnTW), 0, hs, c, s, d, w.S, w.C, g.plane_words, g.wpr);
+    else if (bits && channels == 4) hipLaunchKernelGGL((k_canny_classes<true, 4>), grid, dim3(kCnTW), 0, hs, c, s, d, w.S, w.C, g.plane_words, g.wpr);
+    else if (bits) hipLaunchKernelGGL((k_canny_classes<true, 1>), grid, dim3(kCnTW), 0, hs, c, s, d, w.S, w.C, g.plane_words, g.wpr);
+    else hipLaunchKernelGGL((k_canny_classes<false, 1>), grid, dim3(kCnTW), 0, hs, c, s, d, (u64*)nullptr, (u64*)nullptr, (size_t)0, 0);
     PRL_HIP_CHECK(hipGetLastError());
     return PRL_OK;
 }
@@ -352,12 +370,13 @@ int canny_pages_per_chunk(int n_pages, int W, int H, size_t extra_per_page)
     return stage_chunk(n_pages, canny_work_per_page(W, H) + extra_per_page, (size_t)4 << 30, std::min(65535, by_tiles));
 }
 
-// cv::Canny of n gray pages (a chunk); work: n * canny_work_per_page + kCannyWorkSlack bytes
-int canny_run(const CannyCfg& c, const PageSet& s, const PageSetOut& d, int n, uint8_t* work, unsigned* h_flags, hipStream_t hs)
+// cv::Canny of n pages (a chunk) of 1 channel, or of 3 / 4 with the colour rule; work: n * canny_work_per_page + kCannyWorkSlack bytes
+int canny_run(const CannyCfg& c, const PageSet& s, const PageSetOut& d, int n, uint8_t* work, unsigned* h_flags, hipStream_t hs,
+              int channels = 1)
 {
     const LinkGeom g = link_geom(c.W, c.H);
     const LinkWork w = link_work(g, n, work);
-    const int st = classes_launch(c, true, s, d, n, g, w, hs);
+    const int st = classes_launch(c, true, s, d, n, g, w, hs, channels);
     if (st != PRL_OK) return st;
     return link_and_expand(g, w, n, d, h_flags, nullptr, hs);
 }
@@ -590,6 +609,100 @@ int contour_batch(const PageArgs& a, int channels, float* quads, int32_t* found,
     return doc_batch(a, channels, nullptr, stream, &tail);
 }
 
+// ---- prl::findHoughLineContour (houghLine.cpp:177-256): three medianBlur(3), three medianBlur(5), cv::Canny(25, 50) on the page's
+// own channels, cv::HoughLines(1, pi / 180, 50) (hough.hip), the line filter and the quad search on the host (houghline.h) --------
+
+int hough_edges_checks(const PageArgs& a, int channels, bool with_dst, bool batch)
+{
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
+    if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
+    if ((st = pages_rows_ok(a, channels, with_dst ? 1 : 0, batch)) != PRL_OK) return st;
+    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
+    return with_dst && batch ? pages_overlap_ok(a, channels, 1, false) : PRL_OK;
+}
+
+// What the contour entry hangs on a chunk: the maps stay in the workspace (a.dst is null), tight pages of r256(W * H) bytes at the
+// head of `scratch_per_page` bytes per page behind the edge detector's own work; `run` gets every chunk once its maps are enqueued.
+struct HoughTail {
+    size_t scratch_per_page = 0, small_per_page = 0;
+    std::function<int(int first, int n, uint8_t* tail, const WorkScope& w)> run;
+};
+
+int hough_edges_batch(const PageArgs& a, int channels, void* stream, const HoughTail* tail = nullptr)
+{
+    if (a.n_pages == 0) return PRL_OK;
+    const int W = a.width, H = a.height;
+    const size_t img_bytes = r256((size_t)W * channels * (size_t)H);   // two of them per page: the median passes go to and fro
+    const size_t tail_bytes = tail ? tail->scratch_per_page : 0;
+    const int chunk = canny_pages_per_chunk(a.n_pages, W, H, 2 * img_bytes + tail_bytes);
+    const size_t canny_bytes = r256(canny_work_per_page(W, H) * (size_t)chunk + kCannyWorkSlack);
+    WorkScope w;
+    int st = w.open(stream, (2 * img_bytes + tail_bytes) * (size_t)chunk + canny_bytes, tail ? tail->small_per_page * (size_t)chunk : 0,
+                    canny_pinned_bytes(chunk));
+    if (st != PRL_OK) return st;
+    const hipStream_t hs = w.stream;
+    uint8_t* img0 = w.scratch();
+    uint8_t* img1 = img0 + img_bytes * (size_t)chunk;
+    uint8_t* canny_work = img1 + img_bytes * (size_t)chunk;
+    uint8_t* tail_work = canny_work + canny_bytes;
+    const PageSetOut p0 = page_set_out(img0, img_bytes, (size_t)W * channels), p1 = page_set_out(img1, img_bytes, (size_t)W * channels);
+    const CannyCfg c{W, H, 25, 50};   // houghLine.cpp:215-218
+    for (int first = 0; first < a.n_pages; first += chunk) {
+        const int n = std::min(chunk, a.n_pages - first);
+        PageSet cur = src_pages(a, first);
+        for (int pass = 0; pass < 6; ++pass) {   // houghLine.cpp:199-206
+            const PageSetOut& to = (pass & 1) ? p1 : p0;
+            st = median_pass_pages(W, H, channels, pass < 3 ? 3 : 5, cur, to, n, hs);
+            if (st != PRL_OK) return st;
+            cur = as_source(to);
+        }
+        const PageSetOut maps = tail ? page_set_out(tail_work, r256((size_t)W * (size_t)H), (size_t)W) : dst_pages(a, first);
+        st = canny_run(c, cur, maps, n, canny_work, w.pinned<unsigned>(), hs, channels);
+        if (st != PRL_OK) return st;
+        if (tail && (st = tail->run(first, n, tail_work, w)) != PRL_OK) return st;
+    }
+    return PRL_OK;
+}
+
+int hough_contour_checks(const PageArgs& a, int channels, const int32_t* quads, const int32_t* found, bool batch)
+{
+    const int st = hough_edges_checks(a, channels, false, batch);
+    if (st != PRL_OK) return st;
+    return !quads || !found ? PRL_ERR_BAD_ARG : PRL_OK;
+}
+
+int hough_contour_batch(const PageArgs& a, int channels, int32_t* quads, int32_t* found, int32_t* out_lines, void* stream)
+{
+    if (a.n_pages == 0) return PRL_OK;
+    const HoughPlan p = hough_plan(a.width, a.height);
+    const size_t map_bytes = r256((size_t)a.width * (size_t)a.height);
+    HoughTail tail;
+    tail.scratch_per_page = map_bytes + hough_work_per_page(p);
+    tail.small_per_page = 2 * sizeof(unsigned);
+    std::vector<std::vector<float>> lines;
+    tail.run = [&](int first, int n, uint8_t* maps, const WorkScope& w) -> int {
+        lines.assign((size_t)n, std::vector<float>());
+        // the one read-back of the chunk: the sorted line lists (houghLine.cpp:227-229, threshold 50)
+        const int st = hough_lines_run(p, page_set(maps, map_bytes, (size_t)a.width), n, 50, maps + map_bytes * (size_t)n, w,
+                                       [&](int i, const HlPeak* pk, size_t count) {
+                                           lines[(size_t)i].resize(2 * count);
+                                           for (size_t k = 0; k < count; ++k)
+                                               hl_line_of(pk[k].cell, p.numrho, &lines[(size_t)i][2 * k], &lines[(size_t)i][2 * k + 1]);
+                                       });
+        if (st != PRL_OK) return st;
+        host_pool_for(n, [&](int i) {
+            int32_t* q = quads + (size_t)(first + i) * 8;
+            std::fill(q, q + 8, 0);
+            const int count = (int)std::min<size_t>(lines[(size_t)i].size() / 2, 0x7fffffff);
+            found[first + i] = hl_quad(lines[(size_t)i].data(), count, a.width, a.height, q) ? 1 : 0;
+            if (out_lines) out_lines[first + i] = count;
+        });
+        return PRL_OK;
+    };
+    return hough_edges_batch(a, channels, stream, &tail);
+}
+
 }  // namespace
 }  // namespace prl_hip
 
@@ -773,6 +886,43 @@ int prl_hip_document_contour_host(int channels, const uint8_t* src, size_t src_s
     if (st != PRL_OK) return st;
     return stage_host_pages(a, channels, 1, 1, 1,
                             [&](const PageArgs& page, hipStream_t s) { return contour_batch(page, channels, quad, found, out_try, s); });
+}
+
+int prl_hip_hough_edges_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                     int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
+{
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    const int st = hough_edges_checks(a, channels, true, true);
+    if (st != PRL_OK) return st;
+    return hough_edges_batch(a, channels, stream);
+}
+
+int prl_hip_hough_edges_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
+{
+    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
+    const int st = hough_edges_checks(a, channels, true, false);
+    if (st != PRL_OK) return st;
+    return stage_host_pages(a, channels, 1, width, height, [&](const PageArgs& page, hipStream_t s) { return hough_edges_batch(page, channels, s); });
+}
+
+int prl_hip_hough_line_contour_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                            int width, int height, int32_t* quads, int32_t* found, int32_t* out_lines, void* stream)
+{
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, nullptr, 0, 0};
+    const int st = hough_contour_checks(a, channels, quads, found, true);
+    if (st != PRL_OK) return st;
+    return hough_contour_batch(a, channels, quads, found, out_lines, stream);
+}
+
+int prl_hip_hough_line_contour_host(int channels, const uint8_t* src, size_t src_step, int width, int height, int32_t quad[8], int32_t* found,
+                                    int32_t* out_lines)
+{
+    uint8_t unused = 0;   // the staging helper brings a result down: one byte that nobody reads
+    const PageArgs a{1, src, 0, src_step, width, height, &unused, 0, 1};
+    const int st = hough_contour_checks(a, channels, quad, found, false);
+    if (st != PRL_OK) return st;
+    return stage_host_pages(a, channels, 1, 1, 1,
+                            [&](const PageArgs& page, hipStream_t s) { return hough_contour_batch(page, channels, quad, found, out_lines, s); });
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 //   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
 //   src/warp.h:49-73                                       prl::warpCrop
 //   src/border_detection/autoCrop.h:42-53                  prl::documentContour, prl::autoCrop
+//   src/border_detection/houghLine.h                       prl::findHoughLineContour
 //   src/resize.h:32                                        prl::resize
 //
 // Same names, argument order, defaults, exceptions (std::invalid_argument for an empty image or a bad
@@ -203,6 +204,14 @@ CV_EXPORTS void warpCrop(cv::Mat& inputImage, cv::Mat& outputImage, const std::v
 CV_EXPORTS bool documentContour(cv::Mat& inputImage, const double scaleX, const double scaleY,
                                 std::vector<cv::Point_<float> >& resultContour);
 CV_EXPORTS bool autoCrop(cv::Mat& inputImage, cv::Mat& outputImage);
+
+// src/border_detection/houghLine.h - the reference's second border detector (houghLine.cpp:177-256; the arithmetic is stated in
+// prl_hip.h, "Hough lines"): medianBlur(3) x 3, medianBlur(5) x 3, cv::Canny(25, 50) on the image's own 1, 3 or 4 channels and
+// cv::HoughLines(1, CV_PI / 180, 50) on the device, the line filter and the search for the largest valid quadrilateral on the host.
+// true and the four corners, truncated to int, APPENDED to resultContour as the reference does; false and resultContour untouched.
+// std::invalid_argument("Input image is empty"); cv::Exception StsUnsupportedFormat for a depth other than CV_8U or channels other
+// than 1, 3, 4.  The input's pixels are never written, and no file is (the reference's cv::imwrite calls are debugging leftovers).
+CV_EXPORTS bool findHoughLineContour(cv::Mat& inputImage, std::vector<cv::Point>& resultContour);
 
 // src/resize.h:32 (no defaults, as there) - resize.cpp:29-62 (pyr.hip; the arithmetic is stated in prl_hip.h).  scaleX > 0 and
 // scaleY > 0: cv::resize(INTER_AREA) to cols * scaleX x rows * scaleY, an exact replication through OpenCV's float64 index tables.

@@ -551,6 +551,20 @@ bool prl::autoCrop(cv::Mat& inputImage, cv::Mat& outputImage)
     return true;
 }
 
+// houghLine.cpp:177-256
+bool prl::findHoughLineContour(cv::Mat& inputImage, std::vector<cv::Point>& resultContour)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image is empty");
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::findHoughLineContour: 8-bit images only");
+    int32_t quad[8], found = 0;
+    const int st = prl_hip_hough_line_contour_host(inputImage.channels(), inputImage.data, inputImage.step, inputImage.cols, inputImage.rows,
+                                                   quad, &found, nullptr);
+    if (st != PRL_OK) raise(st);
+    if (!found) return false;
+    for (int i = 0; i < 4; ++i) resultContour.push_back(cv::Point(quad[2 * i], quad[2 * i + 1]));   // :248-251: appended
+    return true;
+}
+
 void prl::resize(const cv::Mat& src, cv::Mat& dst, int scaleX, int scaleY, int maxSize)
 {
     const bool by_scale = scaleX > 0 && scaleY > 0;

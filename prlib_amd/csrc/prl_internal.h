@@ -498,6 +498,20 @@ int pyr_run(int channels, const PageSet& src, int width, int height, int levels,
 // the destination of an entry whose result is out_width x out_height: its rows, and no byte shared with the source
 int resized_dst_ok(const PageArgs& a, int channels, int out_width, int out_height, bool batch);
 
+// ---- cv::HoughLines(rho 1, theta pi / 180) (hough.hip): the sizes of a W x H map's transform, per page and rounded to 256 bytes ----
+struct HoughPlan {
+    int W, H, numrho;
+    int cells, ranges;          // rho cells a workgroup of k_hough_vote keeps in LDS, and how many such ranges a row takes
+    size_t point_cap, points_bytes, accum_cells, accum_bytes, peak_cap, peaks_bytes;
+};
+struct HlPeak;   // houghline.h
+HoughPlan hough_plan(int width, int height);
+size_t hough_work_per_page(const HoughPlan& p);
+// The sorted peaks of n maps (a chunk), page by page through `sink` on the calling thread; work: n * hough_work_per_page bytes,
+// w's `small`: 2 * n words, its pinned block: n words at least (it grows to the lists).  Waits for the stream.
+int hough_lines_run(const HoughPlan& p, const PageSet& maps, int n, int threshold, uint8_t* work, const WorkScope& w,
+                    const std::function<void(int, const HlPeak*, size_t)>& sink);
+
 // ---- morphology (morph.hip) ------------------------------------------------------------------
 int morph_run(int iterations, const PageSet& src, int n_pages, int width, int height,
               const PageSetOut& dst, hipStream_t stream);
