@@ -84,6 +84,23 @@ def _device(pages, oc_of, call, out, gray_only, drop_channel):
     return res
 
 
+def quad_per_page(pages, host_call, device_call, quad_dtype):
+    """A border detector: (quads N x 4 x 2 of quad_dtype, found N bool, a third int32 per page); for one page (a numpy image or a
+    tensor without a page axis) the three without the N.  The calls get the source's arguments as above, then the three results."""
+    host = isinstance(pages, np.ndarray)
+    img, batch = (host_image(pages)[None], False) if host else pages4(pages)[::2]
+    n, h, w, c = img.shape
+    quads, found, third = np.zeros((max(n, 1), 4, 2), quad_dtype), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+    res = (quads.ctypes.data, found.ctypes.data, third.ctypes.data)
+    if host:
+        _capi.check(host_call(c, img.ctypes.data, img.strides[1], w, h, *res))
+    else:
+        _capi.check(device_call(n, c, img.data_ptr(), img.stride(0), img.stride(1), w, h, *res, _capi.stream_on(pages)))
+    if not batch:
+        return quads[0], bool(found[0]), int(third[0])
+    return quads[:n], found[:n].astype(bool), third[:n]
+
+
 def run(pages, oc_of, host_call, device_call, out=None, gray_only=False, drop_channel=False):
     """Dispatch on the kind of `pages`; host_call is None where a function takes device tensors only."""
     if isinstance(pages, np.ndarray) and host_call is not None:

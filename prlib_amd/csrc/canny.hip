@@ -1,9 +1,7 @@
-// canny.hip — cv::Canny (8UC1, apertureSize 3, L1 magnitude) on batched pages and the device half of prl::documentContour
-// (src/border_detection/autoCrop.cpp:67-101): pyramid, most informative channel, edge map.  The arithmetic is stated in
-// include/prl_hip.h ("pyramid, edge map, resize") and restated in tests/edges_ref.py; all of it is integer but the channel choice.
-//
-// The edge map and the contour entry of prl::findHoughLineContour (houghLine.cpp:177-256) are at the end: the only callers of the
-// colour instantiations (CH = 3, 4) of the classes kernel; the public cv::Canny entries keep refusing colour pages.
+// canny.hip — cv::Canny (8UC1, apertureSize 3, L1 magnitude) on batched pages.  The arithmetic is stated in include/prl_hip.h
+// ("pyramid, edge map, resize") and restated in tests/edges_ref.py; all of it is integer.  What the border detectors (border.hip)
+// need of it is declared in prl_internal.h; they are the only callers of the colour instantiations (CH = 3, 4) of the classes
+// kernel: the public cv::Canny entries keep refusing colour pages.
 //
 //   k_canny_classes<BITS, CH>  Sobel, |dx| + |dy|, non-maximum suppression and the two thresholds.  A workgroup owns kCnTW columns and
 //                          walks down kCnRows rows: per source row it stages the clamped pixels (BORDER_REPLICATE) in an LDS ring of
@@ -21,11 +19,7 @@
 //   k_plane_expand         the strong plane as 0 / 255 bytes.
 #include <algorithm>
 #include <cmath>
-#include <cstring>
-#include <vector>
 
-#include "contour.h"
-#include "houghline.h"
 #include "prl_internal.h"
 
 namespace prl_hip {
@@ -256,14 +250,6 @@ __global__ __launch_bounds__(256) void k_plane_expand(const uint8_t* __restrict_
     }
 }
 
-template <int CH>
-__global__ __launch_bounds__(256) void k_take_channel(PageSet src, PageSetOut dst, int W, const int* __restrict__ channel)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y, page = blockIdx.z;
-    if (x >= W) return;
-    dst.page(page)[(size_t)y * dst.step + x] = src.page(page)[(size_t)y * src.step + (size_t)x * CH + channel[page]];
-}
-
 int bad_arg(const char* why)
 {
     set_error_detail(why);
@@ -289,14 +275,6 @@ LinkGeom link_geom(int W, int H)
     g.plane_bytes = g.plane_words * 8;
     return g;
 }
-
-size_t canny_work_per_page(int W, int H)
-{
-    const LinkGeom g = link_geom(W, H);
-    return 2 * g.plane_bytes + 3 * sizeof(unsigned) + 2 * (size_t)g.tiles_x * g.tiles_y;
-}
-constexpr size_t kCannyWorkSlack = 5 * 256;   // the rounding of the five small blocks
-size_t canny_pinned_bytes(int n) { return 2 * sizeof(unsigned) * (size_t)n; }
 
 struct LinkWork {
     u64 *S, *C;
@@ -363,23 +341,7 @@ int link_and_expand(const LinkGeom& g, const LinkWork& w, int n, const PageSetOu
     return PRL_OK;
 }
 
-int canny_pages_per_chunk(int n_pages, int W, int H, size_t extra_per_page)
-{
-    const LinkGeom g = link_geom(W, H);
-    const int by_tiles = (int)std::max<unsigned long long>(1, 0x7fffffffull / ((unsigned long long)g.tiles_x * g.tiles_y));
-    return stage_chunk(n_pages, canny_work_per_page(W, H) + extra_per_page, (size_t)4 << 30, std::min(65535, by_tiles));
-}
-
-// cv::Canny of n pages (a chunk) of 1 channel, or of 3 / 4 with the colour rule; work: n * canny_work_per_page + kCannyWorkSlack bytes
-int canny_run(const CannyCfg& c, const PageSet& s, const PageSetOut& d, int n, uint8_t* work, unsigned* h_flags, hipStream_t hs,
-              int channels = 1)
-{
-    const LinkGeom g = link_geom(c.W, c.H);
-    const LinkWork w = link_work(g, n, work);
-    const int st = classes_launch(c, true, s, d, n, g, w, hs, channels);
-    if (st != PRL_OK) return st;
-    return link_and_expand(g, w, n, d, h_flags, nullptr, hs);
-}
+size_t work_per_page(const LinkGeom& g) { return 2 * g.plane_bytes + 3 * sizeof(unsigned) + 2 * (size_t)g.tiles_x * g.tiles_y; }
 
 // threshold1 / threshold2 as cv::Canny reads them; false: a NaN
 bool canny_thresholds(double t1, double t2, int* low, int* high)
@@ -407,303 +369,40 @@ int canny_batch(const PageArgs& a, int low, int high, void* stream)
     if (a.n_pages == 0) return PRL_OK;
     const int chunk = canny_pages_per_chunk(a.n_pages, a.width, a.height, 0);
     WorkScope w;
-    int st = w.open(stream, canny_work_per_page(a.width, a.height) * (size_t)chunk + kCannyWorkSlack, 0, canny_pinned_bytes(chunk));
+    int st = w.open(stream, canny_work_bytes(chunk, a.width, a.height), 0, canny_pinned_bytes(chunk));
     if (st != PRL_OK) return st;
-    const CannyCfg c{a.width, a.height, low, high};
     for (int first = 0; first < a.n_pages; first += chunk) {
-        st = canny_run(c, src_pages(a, first), dst_pages(a, first), std::min(chunk, a.n_pages - first), w.scratch(), w.pinned<unsigned>(), w.stream);
+        st = canny_run(a.width, a.height, low, high, src_pages(a, first), dst_pages(a, first), std::min(chunk, a.n_pages - first), w.scratch(),
+                       w.pinned<unsigned>(), w.stream);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
-}
-
-void edges_geometry(int W, int H, int* levels, int* ow, int* oh)
-{
-    int n = 0, longSide = std::max(W, H);
-    while (longSide / 2 >= 256) {   // autoCrop.cpp:74-81
-        W = (W + 1) / 2;
-        H = (H + 1) / 2;
-        longSide = std::max(W, H);
-        ++n;
-    }
-    *levels = n;
-    *ow = W;
-    *oh = H;
-}
-
-// the first maximum of cv::meanStdDev's standard deviations, from one page's per-channel bins
-int most_informative_channel(const unsigned* hist, int channels, double pixels)
-{
-    int best = 0;
-    double best_sd = -1;
-    for (int ch = 0; ch < channels; ++ch) {
-        unsigned long long s1 = 0, s2 = 0;
-        for (int v = 0; v < 256; ++v) {
-            s1 += (unsigned long long)hist[ch * 256 + v] * (unsigned)v;
-            s2 += (unsigned long long)hist[ch * 256 + v] * (unsigned)(v * v);
-        }
-        const double mean = (double)s1 / pixels;
-        const double sd = std::sqrt(std::max((double)s2 / pixels - mean * mean, 0.0));
-        if (ch == 0 || best_sd < sd) {   // std::max_element keeps the first of equals
-            best = ch;
-            best_sd = sd;
-        }
-    }
-    return best;
-}
-
-int doc_checks(const PageArgs& a, int channels, const int32_t* out_channel, bool batch)
-{
-    int st = pages_nonempty(a);
-    if (st != PRL_OK) return st;
-    if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
-    if ((st = pages_rows_ok(a, channels, 0, batch)) != PRL_OK) return st;
-    if (!out_channel) return PRL_ERR_BAD_ARG;
-    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
-    int levels, ow, oh;
-    edges_geometry(a.width, a.height, &levels, &ow, &oh);
-    return resized_dst_ok(a, 1, ow, oh, batch);
-}
-
-// What prl::documentContour hangs on a chunk of doc_batch: the maps stay in the workspace (a.dst is null), tight pages of
-// r256(ow * oh) bytes at the head of a tail of `scratch_per_page` bytes per page behind the edge detector's own work, and `run`
-// gets every chunk once its maps are complete and the stream has been waited for; the `small` and pinned blocks are free then.
-struct DocTail {
-    size_t scratch_per_page = 0, small_per_page = 0, pinned_per_page = 0;
-    std::function<int(int first, int n, uint8_t* tail, const WorkScope& w)> run;
-};
-
-int doc_batch(const PageArgs& a, int channels, int32_t* out_channel, void* stream, const DocTail* tail = nullptr)
-{
-    if (a.n_pages == 0) return PRL_OK;
-    int levels, ow, oh;
-    edges_geometry(a.width, a.height, &levels, &ow, &oh);
-    const size_t pyr_bytes = levels ? pyr_work_per_page(a.width, a.height, channels, levels) : 0;
-    const size_t last_bytes = levels ? r256((size_t)ow * channels * (size_t)oh) : 0;   // the last level
-    const size_t gray_bytes = channels > 1 ? r256((size_t)ow * (size_t)oh) : 0;        // the chosen channel
-    const size_t tail_bytes = tail ? tail->scratch_per_page : 0;
-    const int chunk = canny_pages_per_chunk(a.n_pages, ow, oh, pyr_bytes + last_bytes + gray_bytes + tail_bytes);
-    const size_t hist_bytes = channels > 1 ? (size_t)chunk * channels * 256 * sizeof(unsigned) : 0, ch_bytes = sizeof(int) * (size_t)chunk;
-    const size_t canny_bytes = canny_work_per_page(ow, oh) * (size_t)chunk + kCannyWorkSlack;
-    WorkScope w;
-    int st = w.open(stream, (pyr_bytes + last_bytes + gray_bytes + tail_bytes) * (size_t)chunk + r256(canny_bytes),
-                    std::max(channels > 1 ? hist_bytes + ch_bytes : 0, tail ? tail->small_per_page * (size_t)chunk : 0),
-                    std::max(std::max(hist_bytes + ch_bytes, canny_pinned_bytes(chunk)), tail ? tail->pinned_per_page * (size_t)chunk : 0));
-    if (st != PRL_OK) return st;
-    const hipStream_t hs = w.stream;
-    uint8_t* pyr_work = w.scratch();
-    uint8_t* last = pyr_work + pyr_bytes * (size_t)chunk;
-    uint8_t* gray = last + last_bytes * (size_t)chunk;
-    uint8_t* canny_work = gray + gray_bytes * (size_t)chunk;
-    uint8_t* tail_work = canny_work + r256(canny_bytes);
-    const CannyCfg c{ow, oh, 25, 50};   // autoCrop.cpp:99-101
-    for (int first = 0; first < a.n_pages; first += chunk) {
-        const int n = std::min(chunk, a.n_pages - first);
-        PageSet cur = src_pages(a, first);
-        if (levels) {
-            const PageSetOut l = page_set_out(last, last_bytes, (size_t)ow * channels);
-            st = pyr_run(channels, cur, a.width, a.height, levels, l, n, pyr_work, hs);
-            if (st != PRL_OK) return st;
-            cur = as_source(l);
-        }
-        if (channels > 1) {
-            unsigned* d_hist = w.small<unsigned>();
-            int* d_ch = reinterpret_cast<int*>(w.small() + hist_bytes);
-            st = prl_hip_histogram_batch_device(n, channels, cur.base, cur.page_stride, cur.step, ow, oh, d_hist, hs);
-            if (st != PRL_OK) return st;
-            // the one read-back of the call per chunk: the bins come down, the chosen channels go up
-            unsigned* h_hist = w.pinned<unsigned>();
-            int* h_ch = reinterpret_cast<int*>(w.pinned() + hist_bytes);
-            PRL_HIP_CHECK(hipMemcpyAsync(h_hist, d_hist, (size_t)n * channels * 256 * sizeof(unsigned), hipMemcpyDeviceToHost, hs));
-            PRL_HIP_CHECK(hipStreamSynchronize(hs));
-            for (int i = 0; i < n; ++i) {
-                h_ch[i] = most_informative_channel(h_hist + (size_t)i * channels * 256, channels, (double)ow * (double)oh);
-                if (out_channel) out_channel[first + i] = h_ch[i];
-            }
-            PRL_HIP_CHECK(hipMemcpyAsync(d_ch, h_ch, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, hs));
-            const PageSetOut gp = page_set_out(gray, gray_bytes, (size_t)ow);
-            const dim3 grid((unsigned)((ow + 255) / 256), (unsigned)oh, (unsigned)n);
-            if (channels == 3) hipLaunchKernelGGL(k_take_channel<3>, grid, dim3(256), 0, hs, cur, gp, ow, d_ch);
-            else hipLaunchKernelGGL(k_take_channel<4>, grid, dim3(256), 0, hs, cur, gp, ow, d_ch);
-            PRL_HIP_CHECK(hipGetLastError());
-            cur = as_source(gp);
-        } else if (out_channel) {
-            for (int i = 0; i < n; ++i) out_channel[first + i] = 0;
-        }
-        // (canny_run synchronises the stream before it touches the pinned block again: the copy of the channels has left it)
-        const PageSetOut maps = tail ? page_set_out(tail_work, r256((size_t)ow * (size_t)oh), (size_t)ow) : dst_pages(a, first);
-        st = canny_run(c, cur, maps, n, canny_work, w.pinned<unsigned>(), hs);
-        if (st != PRL_OK) return st;
-        if (tail && (st = tail->run(first, n, tail_work, w)) != PRL_OK) return st;
-    }
-    return PRL_OK;
-}
-
-// ---- prl::documentContour: the edge map, the quad search on the host (contour.h), one retry after a closing --------------------
-
-int contour_checks(const PageArgs& a, int channels, const float* quads, const int32_t* found, bool batch)
-{
-    int st = pages_nonempty(a);
-    if (st != PRL_OK) return st;
-    if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
-    if ((st = pages_rows_ok(a, channels, 0, batch)) != PRL_OK) return st;
-    if (!quads || !found) return PRL_ERR_BAD_ARG;
-    return pages_sides_ok(a);
-}
-
-int contour_batch(const PageArgs& a, int channels, float* quads, int32_t* found, int32_t* out_try, void* stream)
-{
-    if (a.n_pages == 0) return PRL_OK;
-    int levels, ow, oh;
-    edges_geometry(a.width, a.height, &levels, &ow, &oh);
-    const int from_w = a.width >> levels, from_h = a.height >> levels;   // autoCrop.cpp:83: cols / 2^levels, not the pyramid's size
-    const size_t map_bytes = r256((size_t)ow * (size_t)oh);
-    DocTail tail;
-    tail.scratch_per_page = 3 * map_bytes;   // the map, then the closing's two planes
-    tail.small_per_page = sizeof(uint8_t*);  // the table of the pages the closing takes
-    tail.pinned_per_page = map_bytes + sizeof(uint8_t*);
-    std::vector<int32_t> corners, again;
-    tail.run = [&](int first, int n, uint8_t* maps, const WorkScope& w) -> int {
-        uint8_t* h_maps = w.pinned();
-        PRL_HIP_CHECK(hipMemcpyAsync(h_maps, maps, map_bytes * (size_t)n, hipMemcpyDeviceToHost, w.stream));
-        PRL_HIP_CHECK(hipStreamSynchronize(w.stream));
-        corners.assign((size_t)n * 8, 0);
-        auto search = [&](int i) {
-            CtPoint q[4];
-            const bool ok = ct_document_quad(h_maps + map_bytes * (size_t)i, (size_t)ow, ow, oh, q);
-            found[first + i] = ok ? 1 : 0;
-            for (int k = 0; ok && k < 4; ++k) {
-                corners[(size_t)i * 8 + 2 * k] = q[k].x;
-                corners[(size_t)i * 8 + 2 * k + 1] = q[k].y;
-            }
-        };
-        host_pool_for(n, search);
-        again.clear();
-        for (int i = 0; i < n; ++i) {
-            if (out_try) out_try[first + i] = found[first + i] ? 0 : 1;
-            if (!found[first + i]) again.push_back(i);
-        }
-        if (!again.empty()) {   // autoCrop.cpp:118-125, first round: CLOSE(2 x 2, iterations 2) on these pages only, in place
-            const int m = (int)again.size();
-            uint8_t** h_table = reinterpret_cast<uint8_t**>(h_maps + map_bytes * (size_t)n);
-            for (int k = 0; k < m; ++k) h_table[k] = maps + map_bytes * (size_t)again[k];
-            uint8_t** d_table = w.small<uint8_t*>();
-            PRL_HIP_CHECK(hipMemcpyAsync(d_table, h_table, sizeof(uint8_t*) * (size_t)m, hipMemcpyHostToDevice, w.stream));
-            const int st = gmorph_close_rect_table_run(2, 2, ow, oh, d_table, (size_t)ow, m, maps + map_bytes * (size_t)n, w.stream);
-            if (st != PRL_OK) return st;
-            for (int k = 0; k < m; ++k)
-                PRL_HIP_CHECK(hipMemcpyAsync(h_maps + map_bytes * (size_t)again[k], h_table[k], (size_t)ow * (size_t)oh, hipMemcpyDeviceToHost,
-                                             w.stream));
-            PRL_HIP_CHECK(hipStreamSynchronize(w.stream));
-            host_pool_for(m, [&](int k) { search(again[k]); });
-        }
-        for (int i = 0; i < n; ++i) {
-            float* out = quads + (size_t)(first + i) * 8;
-            if (!found[first + i] || !ct_finish(&corners[(size_t)i * 8], from_w, from_h, a.width, a.height, out)) {
-                found[first + i] = 0;
-                std::fill(out, out + 8, 0.0f);
-            }
-        }
-        return PRL_OK;
-    };
-    return doc_batch(a, channels, nullptr, stream, &tail);
-}
-
-// ---- prl::findHoughLineContour (houghLine.cpp:177-256): three medianBlur(3), three medianBlur(5), cv::Canny(25, 50) on the page's
-// own channels, cv::HoughLines(1, pi / 180, 50) (hough.hip), the line filter and the quad search on the host (houghline.h) --------
-
-int hough_edges_checks(const PageArgs& a, int channels, bool with_dst, bool batch)
-{
-    int st = pages_nonempty(a);
-    if (st != PRL_OK) return st;
-    if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;
-    if ((st = pages_rows_ok(a, channels, with_dst ? 1 : 0, batch)) != PRL_OK) return st;
-    if ((st = pages_sides_ok(a)) != PRL_OK) return st;
-    return with_dst && batch ? pages_overlap_ok(a, channels, 1, false) : PRL_OK;
-}
-
-// What the contour entry hangs on a chunk: the maps stay in the workspace (a.dst is null), tight pages of r256(W * H) bytes at the
-// head of `scratch_per_page` bytes per page behind the edge detector's own work; `run` gets every chunk once its maps are enqueued.
-struct HoughTail {
-    size_t scratch_per_page = 0, small_per_page = 0;
-    std::function<int(int first, int n, uint8_t* tail, const WorkScope& w)> run;
-};
-
-int hough_edges_batch(const PageArgs& a, int channels, void* stream, const HoughTail* tail = nullptr)
-{
-    if (a.n_pages == 0) return PRL_OK;
-    const int W = a.width, H = a.height;
-    const size_t img_bytes = r256((size_t)W * channels * (size_t)H);   // two of them per page: the median passes go to and fro
-    const size_t tail_bytes = tail ? tail->scratch_per_page : 0;
-    const int chunk = canny_pages_per_chunk(a.n_pages, W, H, 2 * img_bytes + tail_bytes);
-    const size_t canny_bytes = r256(canny_work_per_page(W, H) * (size_t)chunk + kCannyWorkSlack);
-    WorkScope w;
-    int st = w.open(stream, (2 * img_bytes + tail_bytes) * (size_t)chunk + canny_bytes, tail ? tail->small_per_page * (size_t)chunk : 0,
-                    canny_pinned_bytes(chunk));
-    if (st != PRL_OK) return st;
-    const hipStream_t hs = w.stream;
-    uint8_t* img0 = w.scratch();
-    uint8_t* img1 = img0 + img_bytes * (size_t)chunk;
-    uint8_t* canny_work = img1 + img_bytes * (size_t)chunk;
-    uint8_t* tail_work = canny_work + canny_bytes;
-    const PageSetOut p0 = page_set_out(img0, img_bytes, (size_t)W * channels), p1 = page_set_out(img1, img_bytes, (size_t)W * channels);
-    const CannyCfg c{W, H, 25, 50};   // houghLine.cpp:215-218
-    for (int first = 0; first < a.n_pages; first += chunk) {
-        const int n = std::min(chunk, a.n_pages - first);
-        PageSet cur = src_pages(a, first);
-        for (int pass = 0; pass < 6; ++pass) {   // houghLine.cpp:199-206
-            const PageSetOut& to = (pass & 1) ? p1 : p0;
-            st = median_pass_pages(W, H, channels, pass < 3 ? 3 : 5, cur, to, n, hs);
-            if (st != PRL_OK) return st;
-            cur = as_source(to);
-        }
-        const PageSetOut maps = tail ? page_set_out(tail_work, r256((size_t)W * (size_t)H), (size_t)W) : dst_pages(a, first);
-        st = canny_run(c, cur, maps, n, canny_work, w.pinned<unsigned>(), hs, channels);
-        if (st != PRL_OK) return st;
-        if (tail && (st = tail->run(first, n, tail_work, w)) != PRL_OK) return st;
-    }
-    return PRL_OK;
-}
-
-int hough_contour_checks(const PageArgs& a, int channels, const int32_t* quads, const int32_t* found, bool batch)
-{
-    const int st = hough_edges_checks(a, channels, false, batch);
-    if (st != PRL_OK) return st;
-    return !quads || !found ? PRL_ERR_BAD_ARG : PRL_OK;
-}
-
-int hough_contour_batch(const PageArgs& a, int channels, int32_t* quads, int32_t* found, int32_t* out_lines, void* stream)
-{
-    if (a.n_pages == 0) return PRL_OK;
-    const HoughPlan p = hough_plan(a.width, a.height);
-    const size_t map_bytes = r256((size_t)a.width * (size_t)a.height);
-    HoughTail tail;
-    tail.scratch_per_page = map_bytes + hough_work_per_page(p);
-    tail.small_per_page = 2 * sizeof(unsigned);
-    std::vector<std::vector<float>> lines;
-    tail.run = [&](int first, int n, uint8_t* maps, const WorkScope& w) -> int {
-        lines.assign((size_t)n, std::vector<float>());
-        // the one read-back of the chunk: the sorted line lists (houghLine.cpp:227-229, threshold 50)
-        const int st = hough_lines_run(p, page_set(maps, map_bytes, (size_t)a.width), n, 50, maps + map_bytes * (size_t)n, w,
-                                       [&](int i, const HlPeak* pk, size_t count) {
-                                           lines[(size_t)i].resize(2 * count);
-                                           for (size_t k = 0; k < count; ++k)
-                                               hl_line_of(pk[k].cell, p.numrho, &lines[(size_t)i][2 * k], &lines[(size_t)i][2 * k + 1]);
-                                       });
-        if (st != PRL_OK) return st;
-        host_pool_for(n, [&](int i) {
-            int32_t* q = quads + (size_t)(first + i) * 8;
-            std::fill(q, q + 8, 0);
-            const int count = (int)std::min<size_t>(lines[(size_t)i].size() / 2, 0x7fffffff);
-            found[first + i] = hl_quad(lines[(size_t)i].data(), count, a.width, a.height, q) ? 1 : 0;
-            if (out_lines) out_lines[first + i] = count;
-        });
-        return PRL_OK;
-    };
-    return hough_edges_batch(a, channels, stream, &tail);
 }
 
 }  // namespace
+
+// ---- what prl_internal.h declares of this file ---------------------------------------------------------------------------------
+
+size_t canny_work_bytes(int n, int W, int H) { return work_per_page(link_geom(W, H)) * (size_t)n + 5 * 256; }   // (the five small blocks' rounding)
+size_t canny_pinned_bytes(int n) { return 2 * sizeof(unsigned) * (size_t)n; }
+
+int canny_pages_per_chunk(int n_pages, int W, int H, size_t extra_per_page)
+{
+    const LinkGeom g = link_geom(W, H);
+    const int by_tiles = (int)std::max<unsigned long long>(1, 0x7fffffffull / ((unsigned long long)g.tiles_x * g.tiles_y));
+    return stage_chunk(n_pages, work_per_page(g) + extra_per_page, (size_t)4 << 30, std::min(65535, by_tiles));
+}
+
+int canny_run(int W, int H, int low, int high, const PageSet& s, const PageSetOut& d, int n, uint8_t* work, unsigned* h_flags, hipStream_t hs,
+              int channels)
+{
+    const LinkGeom g = link_geom(W, H);
+    const LinkWork w = link_work(g, n, work);
+    const int st = classes_launch(CannyCfg{W, H, low, high}, true, s, d, n, g, w, hs, channels);
+    if (st != PRL_OK) return st;
+    return link_and_expand(g, w, n, d, h_flags, nullptr, hs);
+}
+
 }  // namespace prl_hip
 
 using namespace prl_hip;
@@ -742,7 +441,7 @@ int prl_hip_edge_link_batch_device(int n_pages, const uint8_t* d_classes, size_t
     if (n_pages == 0) return PRL_OK;
     const int chunk = canny_pages_per_chunk(n_pages, width, height, 0);
     WorkScope w;
-    st = w.open(stream, canny_work_per_page(width, height) * (size_t)chunk + kCannyWorkSlack, 0, canny_pinned_bytes(chunk));
+    st = w.open(stream, canny_work_bytes(chunk, width, height), 0, canny_pinned_bytes(chunk));
     if (st != PRL_OK) return st;
     const LinkGeom g = link_geom(width, height);
     for (int first = 0; first < n_pages; first += chunk) {
@@ -777,152 +476,6 @@ int prl_hip_canny_host(int channels, double threshold1, double threshold2, const
     int low, high;
     if (!canny_thresholds(threshold1, threshold2, &low, &high)) return bad_arg("Canny: a threshold is a NaN");
     return stage_host_pages(a, 1, 1, width, height, [&](const PageArgs& page, hipStream_t s) { return canny_batch(page, low, high, s); });
-}
-
-int prl_hip_document_edges_geometry(int width, int height, int* levels, int* out_w, int* out_h)
-{
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (!levels || !out_w || !out_h) return PRL_ERR_BAD_ARG;
-    edges_geometry(width, height, levels, out_w, out_h);
-    return PRL_OK;
-}
-
-int prl_hip_document_edges_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
-                                        int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, int32_t* out_channel,
-                                        void* stream)
-{
-    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
-    const int st = doc_checks(a, channels, out_channel, true);
-    if (st != PRL_OK) return st;
-    return doc_batch(a, channels, out_channel, stream);
-}
-
-int prl_hip_document_edges_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step,
-                                int32_t* out_channel)
-{
-    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
-    const int st = doc_checks(a, channels, out_channel, false);
-    if (st != PRL_OK) return st;
-    int levels, ow, oh;
-    edges_geometry(width, height, &levels, &ow, &oh);
-    return stage_host_pages(a, channels, 1, ow, oh, [&](const PageArgs& page, hipStream_t s) { return doc_batch(page, channels, out_channel, s); });
-}
-
-int prl_hip_find_contours(const uint8_t* map, size_t step, int width, int height, int32_t* points, int max_points, int32_t* contours,
-                          int max_contours, int* n_points, int* n_contours)
-{
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (!map || step < (size_t)width || !n_points || !n_contours || max_points < 0 || max_contours < 0 || (max_points && !points) ||
-        (max_contours && !contours))
-        return PRL_ERR_BAD_ARG;
-    std::vector<CtPoint> pts;
-    std::vector<CtContour> cs;
-    ct_find_contours(map, step, width, height, &pts, &cs);
-    *n_points = (int)pts.size();
-    *n_contours = (int)cs.size();
-    if ((int)pts.size() > max_points || (int)cs.size() > max_contours) return PRL_OK;   // the counts alone: call again with room
-    for (size_t i = 0; i < pts.size(); ++i) {
-        points[2 * i] = pts[i].x;
-        points[2 * i + 1] = pts[i].y;
-    }
-    for (size_t i = 0; i < cs.size(); ++i) {
-        contours[2 * i] = cs[i].count;
-        contours[2 * i + 1] = cs[i].hole;
-    }
-    return PRL_OK;
-}
-
-int prl_hip_approx_poly_closed(const int32_t* points, int n_points, double epsilon, int32_t* out_points, int* n_out)
-{
-    if (n_points < 0 || (n_points && (!points || !out_points)) || !n_out || !(epsilon >= 0)) return PRL_ERR_BAD_ARG;
-    std::vector<CtPoint> src((size_t)n_points), dst((size_t)n_points);
-    for (int i = 0; i < n_points; ++i) src[(size_t)i] = CtPoint{points[2 * i], points[2 * i + 1]};
-    *n_out = ct_approx_closed(src.data(), n_points, epsilon, dst.data());
-    for (int i = 0; i < *n_out; ++i) {
-        out_points[2 * i] = dst[(size_t)i].x;
-        out_points[2 * i + 1] = dst[(size_t)i].y;
-    }
-    return PRL_OK;
-}
-
-int prl_hip_document_quad(const uint8_t* map, size_t step, int width, int height, int32_t quad[8], int* found)
-{
-    if (width <= 0 || height <= 0) return PRL_ERR_EMPTY;
-    if (!map || step < (size_t)width || !quad || !found || width > kStageMaxSide || height > kStageMaxSide) return PRL_ERR_BAD_ARG;
-    CtPoint q[4];
-    *found = ct_document_quad(map, step, width, height, q) ? 1 : 0;
-    for (int k = 0; k < 4; ++k) {
-        quad[2 * k] = *found ? q[k].x : 0;
-        quad[2 * k + 1] = *found ? q[k].y : 0;
-    }
-    return PRL_OK;
-}
-
-int prl_hip_document_quad_finish(const int32_t quad[8], int map_width, int map_height, int src_width, int src_height, float out[8])
-{
-    if (map_width <= 0 || map_height <= 0 || src_width <= 0 || src_height <= 0) return PRL_ERR_EMPTY;
-    if (!quad || !out) return PRL_ERR_BAD_ARG;
-    float r[8];
-    if (!ct_finish(quad, map_width, map_height, src_width, src_height, r)) return PRL_ERR_BAD_ARG;   // not strictly convex
-    std::copy(r, r + 8, out);
-    return PRL_OK;
-}
-
-int prl_hip_document_contour_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
-                                          int height, float* quads, int32_t* found, int32_t* out_try, void* stream)
-{
-    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, nullptr, 0, 0};
-    const int st = contour_checks(a, channels, quads, found, true);
-    if (st != PRL_OK) return st;
-    return contour_batch(a, channels, quads, found, out_try, stream);
-}
-
-int prl_hip_document_contour_host(int channels, const uint8_t* src, size_t src_step, int width, int height, float quad[8], int32_t* found,
-                                  int32_t* out_try)
-{
-    uint8_t unused = 0;   // the staging helper brings a result down: one byte that nobody reads
-    const PageArgs a{1, src, 0, src_step, width, height, &unused, 0, 1};
-    const int st = contour_checks(a, channels, quad, found, false);
-    if (st != PRL_OK) return st;
-    return stage_host_pages(a, channels, 1, 1, 1,
-                            [&](const PageArgs& page, hipStream_t s) { return contour_batch(page, channels, quad, found, out_try, s); });
-}
-
-int prl_hip_hough_edges_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
-                                     int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
-{
-    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
-    const int st = hough_edges_checks(a, channels, true, true);
-    if (st != PRL_OK) return st;
-    return hough_edges_batch(a, channels, stream);
-}
-
-int prl_hip_hough_edges_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
-{
-    const PageArgs a{1, src, 0, src_step, width, height, dst, 0, dst_step};
-    const int st = hough_edges_checks(a, channels, true, false);
-    if (st != PRL_OK) return st;
-    return stage_host_pages(a, channels, 1, width, height, [&](const PageArgs& page, hipStream_t s) { return hough_edges_batch(page, channels, s); });
-}
-
-int prl_hip_hough_line_contour_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
-                                            int width, int height, int32_t* quads, int32_t* found, int32_t* out_lines, void* stream)
-{
-    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, nullptr, 0, 0};
-    const int st = hough_contour_checks(a, channels, quads, found, true);
-    if (st != PRL_OK) return st;
-    return hough_contour_batch(a, channels, quads, found, out_lines, stream);
-}
-
-int prl_hip_hough_line_contour_host(int channels, const uint8_t* src, size_t src_step, int width, int height, int32_t quad[8], int32_t* found,
-                                    int32_t* out_lines)
-{
-    uint8_t unused = 0;   // the staging helper brings a result down: one byte that nobody reads
-    const PageArgs a{1, src, 0, src_step, width, height, &unused, 0, 1};
-    const int st = hough_contour_checks(a, channels, quad, found, false);
-    if (st != PRL_OK) return st;
-    return stage_host_pages(a, channels, 1, 1, 1,
-                            [&](const PageArgs& page, hipStream_t s) { return hough_contour_batch(page, channels, quad, found, out_lines, s); });
 }
 
 }  // extern "C"

@@ -286,11 +286,10 @@ int prl_hip_hough_lines_batch_device(int n_pages, const uint8_t* d_map, size_t p
 int prl_hip_hough_lines_host(const uint8_t* map, size_t step, int width, int height, int threshold, float* lines, int max_lines,
                              int32_t* n_lines)
 {
-    uint8_t unused = 0;   // the staging helper brings a result down: one byte that nobody reads
-    const PageArgs a{1, map, 0, step, width, height, &unused, 0, 1};
+    const PageArgs a{1, map, 0, step, width, height, nullptr, 0, 0};
     const int st = lines_checks(a, threshold, lines, max_lines, n_lines, false);
     if (st != PRL_OK) return st;
-    return stage_host_pages(a, 1, 1, 1, 1,
+    return stage_host_pages(a, 1, 0, 0, 0,
                             [&](const PageArgs& page, hipStream_t s) { return lines_batch(page, threshold, lines, max_lines, n_lines, s); });
 }
 

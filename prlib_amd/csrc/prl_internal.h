@@ -295,6 +295,7 @@ inline PageSetOut dst_pages(const PageArgs& a, int first) { return pages_from(pa
 // 256-byte offsets, rows packed tightly; the source goes up, then
 //     int run(const PageArgs& page, hipStream_t stream)
 // gets the staging area as a one-page batch of the same width and height on the null stream, and the result comes down into h.dst.
+// An entry whose result is not a page leaves h.dst null (and the three out_* zero): no [out], a null destination, no download.
 template <typename Run>
 int stage_host_pages(const PageArgs& h, int in_channels, int out_channels, int out_width, int out_height, Run&& run)
 {
@@ -303,20 +304,20 @@ int stage_host_pages(const PageArgs& h, int in_channels, int out_channels, int o
     if (st != PRL_OK) return st;
     DeviceCtx* ctx = device_ctx(dev);
     const size_t in_row = (size_t)h.width * in_channels, out_row = (size_t)out_width * out_channels;
-    const size_t in_bytes = r256(in_row * (size_t)h.height), out_bytes = r256(out_row * (size_t)out_height);
+    const size_t in_bytes = r256(in_row * (size_t)h.height), out_bytes = h.dst ? r256(out_row * (size_t)out_height) : 0;
     std::lock_guard<std::mutex> slk(ctx->stage_mu);  // cached device + pinned staging: no allocation per page (lock order: stage_mu, then mu)
     st = ensure_stage(ctx, in_bytes + out_bytes);
     if (st != PRL_OK) return st;
     st = ensure_stage_pinned(ctx, in_bytes + out_bytes);
     if (st != PRL_OK) return st;
     uint8_t* d_in = static_cast<uint8_t*>(ctx->stage);
-    uint8_t* d_out = d_in + in_bytes;
+    uint8_t* d_out = h.dst ? d_in + in_bytes : nullptr;
     const hipStream_t stream = nullptr;
     DrainOnExit drain_guard{stream};
     st = stage_upload(ctx, 0, h.src, h.src_step, in_row, h.height, d_in, stream);
     if (st != PRL_OK) return st;
     st = run(PageArgs{1, d_in, in_bytes, in_row, h.width, h.height, d_out, out_bytes, out_row}, stream);
-    if (st != PRL_OK) return st;
+    if (st != PRL_OK || !h.dst) return st;
     return stage_download(ctx, in_bytes, d_out, out_row, out_height, h.dst, h.dst_step, stream);
 }
 
@@ -480,7 +481,7 @@ int gmorph_open_rect_run(int kw, int kh, int width, int height, const PageSet& s
 int gmorph_dilate_rect_run(int k, int width, int height, const PageSet& src, const PageSetOut& dst, int n_pages, uint8_t* tmp,
                            hipStream_t stream);
 // CLOSE with a k x k rectangle, default anchor, `iterations` times, IN PLACE on the 1-channel pages a DEVICE table of page
-// pointers names (rows `step` bytes apart): the border detector's retry on the pages without a quad (canny.hip).  `tmp`:
+// pointers names (rows `step` bytes apart): the border detector's retry on the pages without a quad (border.hip).  `tmp`:
 // 2 * n_pages * width * height bytes; enqueues only (caller holds ctx->mu)
 int gmorph_close_rect_table_run(int k, int iterations, int width, int height, uint8_t* const* d_table, size_t step, int n_pages,
                                 uint8_t* tmp, hipStream_t stream);
@@ -497,6 +498,15 @@ int pyr_run(int channels, const PageSet& src, int width, int height, int levels,
             hipStream_t stream);
 // the destination of an entry whose result is out_width x out_height: its rows, and no byte shared with the source
 int resized_dst_ok(const PageArgs& a, int channels, int out_width, int out_height, bool batch);
+
+// ---- cv::Canny (canny.hip) of n pages (a chunk) of W x H: 1 channel, or 3 / 4 with the colour rule of prl::findHoughLineContour,
+// into 0 / 255 maps.  work: canny_work_bytes(n, W, H); h_flags: pinned, canny_pinned_bytes(n).  Synchronises the stream (caller
+// holds ctx->mu).  canny_pages_per_chunk: the pages a chunk takes when a page costs extra_per_page bytes beside Canny's own ------
+size_t canny_work_bytes(int n, int W, int H);
+size_t canny_pinned_bytes(int n);
+int canny_pages_per_chunk(int n_pages, int W, int H, size_t extra_per_page);
+int canny_run(int W, int H, int low, int high, const PageSet& src, const PageSetOut& dst, int n, uint8_t* work, unsigned* h_flags,
+              hipStream_t stream, int channels = 1);
 
 // ---- cv::HoughLines(rho 1, theta pi / 180) (hough.hip): the sizes of a W x H map's transform, per page and rounded to 256 bytes ----
 struct HoughPlan {

@@ -200,21 +200,7 @@ def document_contour(pages):
     """prl::documentContour(page, -1, -1, contour) per page -> (quads N x 4 x 2 float32, found N bool, tries N int32); for one
     page (a numpy image or a tensor without a page axis) the three without the N."""
     L = _capi.lib()
-    if isinstance(pages, np.ndarray):
-        img = _pages.host_image(pages)
-        h, w, c = img.shape
-        quads, found, tries = np.zeros((1, 4, 2), np.float32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        _capi.check(L.prl_hip_document_contour_host(c, img.ctypes.data, img.strides[0], w, h, quads.ctypes.data, found.ctypes.data,
-                                                    tries.ctypes.data))
-        return quads[0], bool(found[0]), int(tries[0])
-    t4, _chan, batch = _pages.pages4(pages)
-    n, h, w, c = t4.shape
-    quads, found, tries = np.zeros((max(n, 1), 4, 2), np.float32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-    _capi.check(L.prl_hip_document_contour_batch_device(n, c, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h, quads.ctypes.data,
-                                                        found.ctypes.data, tries.ctypes.data, _capi.stream_on(pages)))
-    if not batch:
-        return quads[0], bool(found[0]), int(tries[0])
-    return quads[:n], found[:n].astype(bool), tries[:n]
+    return _pages.quad_per_page(pages, L.prl_hip_document_contour_host, L.prl_hip_document_contour_batch_device, np.float32)
 
 
 def auto_crop(pages, return_contour: bool = False):

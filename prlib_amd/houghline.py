@@ -99,18 +99,4 @@ def hough_line_contour(pages):
     """prl::findHoughLineContour per page -> (quads N x 4 x 2 int32, found N bool, lines N int32: what cv::HoughLines found); for
     one page (a numpy image or a tensor without a page axis) the three without the N."""
     L = _capi.lib()
-    if isinstance(pages, np.ndarray):
-        img = _pages.host_image(pages)
-        h, w, c = img.shape
-        quads, found, lines = np.zeros((1, 4, 2), np.int32), np.zeros(1, np.int32), np.zeros(1, np.int32)
-        _capi.check(L.prl_hip_hough_line_contour_host(c, img.ctypes.data, img.strides[0], w, h, quads.ctypes.data, found.ctypes.data,
-                                                      lines.ctypes.data))
-        return quads[0], bool(found[0]), int(lines[0])
-    t4, _chan, batch = _pages.pages4(pages)
-    n, h, w, c = t4.shape
-    quads, found, lines = np.zeros((max(n, 1), 4, 2), np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
-    _capi.check(L.prl_hip_hough_line_contour_batch_device(n, c, t4.data_ptr(), t4.stride(0), t4.stride(1), w, h, quads.ctypes.data,
-                                                          found.ctypes.data, lines.ctypes.data, _capi.stream_on(pages)))
-    if not batch:
-        return quads[0], bool(found[0]), int(lines[0])
-    return quads[:n], found[:n].astype(bool), lines[:n]
+    return _pages.quad_per_page(pages, L.prl_hip_hough_line_contour_host, L.prl_hip_hough_line_contour_batch_device, np.int32)

@@ -338,6 +338,6 @@ def test_exports_maps_and_python(prl):
     for fn in ("pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize",
                "resize_pyramid_levels"):
         assert callable(getattr(prl, fn)) and fn in prl.__all__
-    for f in ("pyr.hip", "canny.hip"):
+    for f in ("pyr.hip", "canny.hip", "border.hip"):
         assert f in open(os.path.join(ROOT, "prlib_amd", "csrc", "Makefile")).read()
         assert f[:-4] in re.search(r"set\(PRL_KERNELS ([^)]*)\)", open(os.path.join(ROOT, "CMakeLists.txt")).read()).group(1).split()

@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_five_pages_in_chunks_of_two(prl, cuda_device):
     """Every batched result is byte for byte the stack of the five single-page calls of the same process (one page is one chunk
-    whatever the knob says); median, removeLines and the tone functions also equal their restatements.  Thinning, the
+    whatever the knob says); median, removeLines, the tone functions, cv::Canny with its two stages, cv::pyrDown and the edge map
+    of prl::documentContour (with the channel it chose per page) also equal their restatements.  Thinning, the
     local-variance binarizers, denoise, backgroundNormalization, the mask morphology (fused and large radius) and rotate go
     through their C entries on the strided pages, on inputs whose results are neither constant nor equal between pages.  All outputs are integers: zero differing bytes, no tolerance."""
     code = r'''
@@ -73,9 +74,39 @@ each("histogram", lambda p: P.histogram(p), (1, 3), lambda p: tone_ref.histogram
 each("binarizeMokji", lambda p: P.binarizeMokji(p), (1, 3))
 each("mokjiThresholds", lambda p: P.mokjiThresholds(p), (1, 3))
 
+import edges_ref
+from prlib_amd import edges as E
+each("canny", lambda p: E.canny(p, 25, 50), (1,), lambda p: edges_ref.canny(p, 25.0, 50.0))
+each("canny_classes", lambda p: E.canny_classes(p, 25, 50), (1,), lambda p: edges_ref.canny_classes(p, 25.0, 50.0))
+each("edge_link", lambda p: E.edge_link(E.canny_classes(p, 25, 50)), (1,), lambda p: edges_ref.edge_link(edges_ref.canny_classes(p, 25.0, 50.0)))
+each("pyr_down", lambda p: E.pyr_down(p, 1), (1, 3), lambda p: edges_ref.pyr_down(p, 1))
+
+# document_edges: 520 / 2 >= 256, the smallest page that takes a pyramid level (the map is 260 x 20).  Smooth blobs, others on
+# every page, under a little noise; on the colour pages channel i % 3 has the full contrast, the others a quarter of it
+DW, DH = 520, 40
+yy, xx = np.mgrid[0:DH, 0:DW]
+for c in (1, 3):
+    buf = np.zeros((N, DH + 8, DW + 24) + ((c,) if c > 1 else ()), np.uint8)
+    for i in range(N):
+        g = (128 + 100 * np.sin(xx / (9.0 + 2 * i)) * np.cos(yy / (5.0 + i)) + rng.integers(-6, 7, size=(DH, DW))).astype(np.uint8)
+        g[8 + 3 * i:20 + 3 * i, 40 + 50 * i:200 + 50 * i] = 250 - 40 * i
+        buf[i, 2:2 + DH, 7:7 + DW] = g if c == 1 else np.stack([g if k == i % 3 else (g >> 2) + 90 for k in range(3)], axis=2)
+    pages = torch.from_numpy(buf).cuda()[:, 2:2 + DH, 7:7 + DW]
+    assert pages.stride(0) > DH * DW * c and pages.stride(1) > DW * c
+    hp = pages.cpu().numpy()
+    want = [edges_ref.document_edges(p) for p in hp]
+    if c == 3:
+        chosen = [edges_ref.most_informative_channel(edges_ref.pyr_down(p, 1)) for p in hp]
+        assert chosen == [w[1] for w in want] and len(set(chosen)) > 1, chosen
+    maps, channels = E.document_edges(pages)
+    singles = [E.document_edges(pages[i]) for i in range(N)]
+    assert maps.shape == (N, 20, 260) and len({m.cpu().numpy().tobytes() for m, _ in singles}) == N
+    same("document_edges c=%d" % c, maps, [m for m, _ in singles], [w[0] for w in want])
+    assert channels.dtype == np.int32 and list(channels) == [ch for _, ch in singles] == [w[1] for w in want], (c, channels)
+
 for c in (1, 3):   # a table set per page
     pages = gray if c == 1 else colour
-    tables = rng.integers(0, 256, size=(N, c, 256), dtype=np.uint8)
+    tables =rng.integers(0, 256, size=(N, c, 256), dtype=np.uint8)
     td = torch.from_numpy(tables).cuda()
     same("lut c=%d" % c, P.lut(pages, td), [P.lut(pages[i], td[i]) for i in range(N)], [tone_ref.apply_luts(host[c][i], tables[i]) for i in range(N)])
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""cv::pyrDown, cv::Canny, the edge map of prl::documentContour and prl::resize (pyr.hip, canny.hip) on device-resident pages:
+"""cv::pyrDown, cv::Canny, the edge map of prl::documentContour and prl::resize (pyr.hip, canny.hip, border.hip) on device-resident pages:
 one JSON line per case.
 
     python tools/bench_edges.py [--steps 5] [--warmup 2] [--repeats 5] [--only P1,P2,C1,C2,D1,R1] [--out FILE] [--no-check]
