@@ -9,7 +9,7 @@
 // rows of 64-bit words, bit b of word k = pixel 64 k + b, rows padded to whole words (the pad bits are 0 in memory).
 //   k_ln_hist<C>  256-bin histogram of gray per page (LDS-privatised; a wavefront whose pixels are all equal adds once).
 //                 For 3 channels the luma is computed here and the gray page is written to scratch for the mask pass.
-//   k_ln_otsu     getThreshVal_Otsu_8u's float64 scan (k_otsu of deskew.hip) over the REVERSED bins = the histogram of inv;
+//   k_ln_otsu     getThreshVal_Otsu_8u's float64 scan (k_otsu of ppht.hip) over the REVERSED bins = the histogram of inv;
 //                 leaves g = 255 - t per page on the device, so that bw = gray < g.
 //   k_ln_mask     a wavefront ballot per 64 pixels -> one word of the bw plane.
 //   k_ln_hopen    horizontal opening.  A workgroup keeps whole rows in LDS, loaded shifted by 2 (L/2) bits so that no step

@@ -26,6 +26,8 @@ struct PageArgs {
 
 constexpr int kStageMaxSide = 32768;
 
+inline size_t r256(size_t v) { return (v + 255) / 256 * 256; }   // sizes and offsets of 256-byte aligned blocks
+
 inline int pages_nonempty(const PageArgs& a) { return a.width <= 0 || a.height <= 0 ? PRL_ERR_EMPTY : PRL_OK; }
 
 // null pointers and steps below the row bytes; a negative page count where the entry takes one (`batch`).  out_channels == 0:

@@ -3,7 +3,7 @@
 //
 // Reference: src/deskew/deskew.cpp:148 (cv::HoughLinesP(input, lines, 1, CV_PI/180, 100, width/8.f, 20)); OpenCV's
 // HoughLinesProbabilistic [upstream] as restated in the test oracle (oracle/, deskew file).  Same segments, in the same order, as
-// k_ppht / k_ppht_mw (deskew.hip), which keep the accumulator in device memory and are bound by the rate of scattered
+// k_ppht / k_ppht_mw (ppht.hip), which keep the accumulator in device memory and are bound by the rate of scattered
 // read-modify-writes one CU gets through its miss path (0.6 us per point: DESIGN.md 4.4).
 //
 // What makes the transform sequential is only this: a point votes into the cells the earlier points left, and when a cell reaches
@@ -34,7 +34,7 @@
 //
 // Safety: workgroups of a group wait for each other, so all of them must be resident: the launch is cooperative and sized by the
 // occupancy query.  Every spin is bounded by a wall-clock budget (s_memrealtime); a member that runs out raises the group's abort
-// word and every member leaves; pages not marked done are redone by k_ppht_mw in the same process (deskew.hip).
+// word and every member leaves; pages not marked done are redone by k_ppht_mw in the same process (ppht.hip).
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -165,7 +165,7 @@ __global__ void __launch_bounds__(256) k_order_resolve(const unsigned* __restric
     order[off + t] = nz[off + p];
 }
 
-// byte mask (k_dark_mask of deskew.hip) -> 1 bit per pixel, rows of `rowwords` dwords; one wavefront per row
+// byte mask (k_dark_mask of ppht.hip) -> 1 bit per pixel, rows of `rowwords` dwords; one wavefront per row
 __global__ void __launch_bounds__(64) k_pack_bits(int width, int height, const uint8_t* __restrict__ mask, size_t mask_page,
                                                   unsigned* __restrict__ bits, size_t mask_words, int rowwords)
 {
@@ -750,7 +750,7 @@ bool ppht_group_eligible(int width, int height, int threshold)
 }
 
 /*
- * Runs the group kernel over the pages of `page_list` (indices into the pass; heaviest first).  The caller (ppht_pages, deskew.hip)
+ * Runs the group kernel over the pages of `page_list` (indices into the pass; heaviest first).  The caller (ppht_pages, ppht.hip)
  * has produced the byte masks, the point lists, counts and offsets and the segment lists' layout; status[i] = 1 for every page that was
  * finished here - the caller redoes the others.  Enqueues on `stream`, does not synchronise.
  */
@@ -767,7 +767,7 @@ int ppht_group_run(DeviceCtx* ctx, PphtGroupIn& in, hipStream_t stream)
     PRL_HIP_CHECK(hipDeviceGetAttribute(&max_lds, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
     max_lds = std::max(max_lds, 160 * 1024);   // gfx950: 160 KB per CU, all of it available to one workgroup
     const size_t lds_budget = (size_t)max_lds - fa.sharedSizeBytes - 256;
-    GroupPlan gp = plan_group(W, H, in.threshold, in.h_ttab, lds_budget, knobs.ppht_group_g);
+    GroupPlan gp = plan_group(W, H, in.threshold, in.pass.h_ttab, lds_budget, knobs.ppht_group_g);
     if (gp.G == 0) return PRL_ERR_BAD_ARG;
     const int G = gp.G;
     PRL_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_ppht_group), hipFuncAttributeMaxDynamicSharedMemorySize, (int)gp.lds_bytes));
@@ -796,8 +796,8 @@ int ppht_group_run(DeviceCtx* ctx, PphtGroupIn& in, hipStream_t stream)
     size_t nz_total = 0;
     unsigned max_n = 0;
     for (int i = 0; i < n_pages; ++i) {
-        nz_total = std::max<size_t>(nz_total, (size_t)in.h_nzoff[(size_t)i] + (in.h_count[(size_t)i] + 63) / 64 * 64);
-        max_n = std::max(max_n, in.h_count[(size_t)i]);
+        nz_total = std::max<size_t>(nz_total, (size_t)in.pass.h_nzoff[(size_t)i] + (in.pass.h_count[(size_t)i] + 63) / 64 * 64);
+        max_n = std::max(max_n, in.pass.h_count[(size_t)i]);
     }
     // workspace: bit masks (shared + private), linked lists, order, random numbers, tables, mailboxes
     const size_t b_mask0 = r256(mask_words * 4 * (size_t)n_pages), b_pmask = r256(mask_words * 4 * (size_t)grid);
@@ -859,7 +859,7 @@ int ppht_group_run(DeviceCtx* ctx, PphtGroupIn& in, hipStream_t stream)
     // 16.16 fixed point)
     int4* k_ltab = reinterpret_cast<int4*>(k_pl + (size_t)n_list * 4);
     for (int n = 0; n < kNumAngle; ++n) {
-        const float fa = -in.h_ttab[2 * n + 1], fb = in.h_ttab[2 * n];
+        const float fa = -in.pass.h_ttab[2 * n + 1], fb = in.pass.h_ttab[2 * n];
         int4 lt{0, 0, 0, 0};
         if (std::fabs((double)fa) > std::fabs((double)fb)) {
             lt.x = 1;
@@ -880,10 +880,10 @@ int ppht_group_run(DeviceCtx* ctx, PphtGroupIn& in, hipStream_t stream)
     PRL_HIP_CHECK(hipMemsetAsync(d_head, 0xff, nz_total * 4, stream));
     if (max_n) {
         const dim3 og((max_n + 255) / 256, (unsigned)n_pages);
-        hipLaunchKernelGGL(k_order_link, og, dim3(256), 0, stream, d_rnd, in.d_count, in.d_nzoff, d_head, d_next);
-        hipLaunchKernelGGL(k_order_resolve, og, dim3(256), 0, stream, d_rnd, in.d_count, in.d_nzoff, d_head, d_next, in.d_nz, d_order);
+        hipLaunchKernelGGL(k_order_link, og, dim3(256), 0, stream, d_rnd, in.pass.d_count, in.pass.d_nzoff, d_head, d_next);
+        hipLaunchKernelGGL(k_order_resolve, og, dim3(256), 0, stream, d_rnd, in.pass.d_count, in.pass.d_nzoff, d_head, d_next, in.pass.d_nz, d_order);
     }
-    hipLaunchKernelGGL(k_pack_bits, dim3((unsigned)H, (unsigned)n_pages), dim3(64), 0, stream, W, H, in.d_mask, in.mask_page, d_mask0,
+    hipLaunchKernelGGL(k_pack_bits, dim3((unsigned)H, (unsigned)n_pages), dim3(64), 0, stream, W, H, in.pass.d_mask, in.pass.mask_page, d_mask0,
                        mask_words, rowwords);
     PRL_HIP_CHECK(hipGetLastError());
     if (in.ev[0]) PRL_HIP_CHECK(hipEventRecord(in.ev[0], stream));
@@ -892,9 +892,9 @@ int ppht_group_run(DeviceCtx* ctx, PphtGroupIn& in, hipStream_t stream)
     a.width = W; a.height = H; a.threshold = in.threshold; a.line_length = in.line_length; a.line_gap = in.line_gap;
     a.G = G; a.n_groups = n_groups; a.xcd_aligned = xcd ? 1 : 0; a.n_list = n_list;
     a.rowwords = rowwords; a.mask_words = mask_words; a.mask0 = d_mask0; a.pmask = d_pmask;
-    a.order = d_order; a.nz_off = in.d_nzoff; a.count = in.d_count;
-    a.tab = d_tab; a.tab_n = d_tabn; a.tab_dwords = d_tabdw; a.ttab = in.d_ttab; a.ltab = d_ltab;
-    a.lines = in.d_lines; a.lines_off = in.d_lnoff; a.lines_cap = in.d_cap; a.n_lines = in.d_nlines;
+    a.order = d_order; a.nz_off = in.pass.d_nzoff; a.count = in.pass.d_count;
+    a.tab = d_tab; a.tab_n = d_tabn; a.tab_dwords = d_tabdw; a.ttab = in.pass.d_ttab; a.ltab = d_ltab;
+    a.lines = in.pass.d_lines; a.lines_off = in.pass.d_lnoff; a.lines_cap = in.pass.d_cap; a.n_lines = in.pass.d_nlines;
     a.mbox = d_mbox; a.abort_word = d_abort; a.queue = d_queue; a.page_list = d_pl; a.status = d_status;
     a.spin_budget = (unsigned long long)std::max(1, knobs.ppht_group_spin_ms) * 100000ull;
     a.kill_group = knobs.ppht_group_kill >= 0 ? 0 : -1;

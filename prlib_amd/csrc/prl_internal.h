@@ -33,8 +33,6 @@ void set_error_detail(const std::string& s);
 
 struct StreamWs;  // per-(device, stream) workspace of the binarizers (prl_capi.hip)
 
-inline size_t r256(size_t v) { return (v + 255) / 256 * 256; }   // sizes and offsets of 256-byte aligned blocks
-
 // ---- per-device context: cached scratch memory ------------------------------------------------
 struct DeviceCtx {
     std::mutex streams_mu;  // guards `streams` only (never held across device work: deskew holds `mu` for seconds)
@@ -150,6 +148,13 @@ private:
 
 int current_device(int* dev);             // validates that a gfx950 device is usable
 DeviceCtx* device_ctx(int dev);
+inline int current_ctx(DeviceCtx** ctx)   // the two in sequence: the current device's context
+{
+    int dev;
+    const int st = current_device(&dev);
+    if (st == PRL_OK) *ctx = device_ctx(dev);
+    return st;
+}
 // Grow-only cached buffers, one pair per memory kind: device (hipMalloc) and pinned host (hipHostMalloc).  A buffer that has to
 // grow is freed once the whole device has drained, then allocated anew; free_* leave {nullptr, 0} behind.
 int ensure_buffer(void** buf, size_t* have, size_t bytes);
@@ -170,7 +175,8 @@ int device_acquire(DeviceCtx* ctx, hipStream_t stream);
 // after the device check, before anything is allocated, calls them apart (thin.hip).  On every exit after a successful grow(),
 // error exits included, the call's work is recorded as the new last use before `mu` is released.
 // Not on it, each with a workspace and lock of its own: deskew.hip's host_roundtrip (its own buffers, a result size per page),
-// the find_angle / houghp entries and everything else under `ppht_mu`.
+// and the angle search under `ppht_mu` (ppht.hip; deskew_find and deskew_ink_census of deskew.hip), which the chain runs beside
+// the stages that are on it.  The deskew, find_angle and houghp entries do share the check pieces of page_args.h.
 enum class NlmTables { kDrop, kKeep };   // (a type of its own: no size can be passed in its place)
 constexpr NlmTables kKeepNlmTables = NlmTables::kKeep;
 class WorkScope {
@@ -410,10 +416,34 @@ int denoise_nlm(DeviceCtx* ctx, int cnt, float strength, uint8_t* planes, int wi
 int denoise_convert_out(DeviceCtx* ctx, int cnt, int channels, const uint8_t* planes, int width, int height, const PageSetOut& dst,
                         hipStream_t s);
 
+// ---- prl::rotate (rotate.hip): one record per page, as the host fills it and k_warp / k_rot90 read it ------
+struct WarpPage {
+    double M[6];   // the inverted matrix warpAffine works with
+    int kind;      // 0 warp, 1/2/3 = 90/180/270, 4 = copy (deskew without an angle)
+    int ow, oh;
+};
+// the record of a width x height page turned by `angle` degrees (copy: left as it is), its result size included
+void fill_warp_page(int width, int height, double angle, bool copy, WarpPage* wp);
+// every page by its record (d_wp: device); max_ow x max_oh: the largest result.  any_quarter = false: no page is of kind 1 / 3.
+// Enqueues only.
+int launch_warp(int channels, const PageSet& s, const PageSetOut& d, int width, int height, int n_pages, int max_ow, int max_oh,
+                const WarpPage* d_wp, hipStream_t stream, bool any_quarter = true);
+
+// ---- HoughLinesP and findAngle (ppht.hip) ------
+// Otsu's threshold of n_pages 1-channel pages into d_thr, by way of their histograms (d_hist: 256 words per page); enqueues only
+int otsu_thresholds(const PageSet& gray, int width, int height, int n_pages, unsigned* d_hist, int* d_thr, hipStream_t stream);
+struct SearchStart;
+// The segments findAngle's cv::HoughLinesP(1, CV_PI/180, 100, width/8.f, 20) finds on `cnt` 1-channel pages (a contiguous batch),
+// per page in `lines` (host, 4 ints each).  Points are the pixels at or below the page's Otsu threshold (prl::deskew's gray page)
+// or, otsu = false, below 255 (findAngle's binarized page).  Synchronises `hs`; the caller holds ctx->ppht_mu.
+int find_angle_segments(DeviceCtx* ctx, int cnt, const PageSet& gray, int width, int height, bool otsu,
+                        std::vector<std::vector<int>>* lines, hipStream_t hs, SearchStart* start);
+double vote_angle(const int* segments, int n_segments);   // findAngle's vote over one page's segments, in degrees
+
 // ---- deskew (deskew.hip): one pass over `cnt` pages, as its two halves (the chain overlaps them) or in one go ------
 int deskew_pages_per_pass(int n_pages, int width, int height);
 struct DeskewPlan {                   // what the angle search of a pass hands to its rotation
-    std::vector<unsigned char> warp;  // one WarpPage record per page (deskew.hip)
+    std::vector<WarpPage> warp;       // one record per page
     std::vector<int32_t> wh;          // result size per page
     std::vector<double> angles;       // findAngle's degrees per page
     int max_ow = 0, max_oh = 0;
@@ -445,15 +475,26 @@ int deskew_apply(DeviceCtx* ctx, const DeskewPlan& plan, int cnt, int channels, 
                  const PageSetOut& dst, hipStream_t hs);
 int deskew_pages(DeviceCtx* ctx, int cnt, int channels, const PageSet& src, int width, int height, const PageSetOut& dst,
                  int32_t* out_wh, double* angles, hipStream_t hs);
-// ppht_group.hip: HoughLinesP's second stage with the accumulator in LDS, a group of workgroups per page.  Device pointers are
-// those of ppht_pages' workspace (deskew.hip); the host arrays must stay alive until the stream has been synchronised.
+// One page at a time host -> device -> host around a device-side stage whose result has a size of its own (the *_host entries of
+// deskew, rotate and find_angle): h describes the host page; `stage` gets it as a one-page batch in buffers of this call's own,
+// the destination max_w x max_h, and leaves the result's size in *out_w / *out_h, against which h.dst_step is then checked.
+// h.dst null: nothing comes down (no destination for the stage, out_w / out_h unused).  Takes stage_mu around the two copies.
+int host_roundtrip(const PageArgs& h, int channels, int max_w, int max_h, const int* out_w, const int* out_h,
+                   const std::function<int(const PageArgs&, hipStream_t)>& stage);
+// The lists of one pass of the search (ppht.hip), device pointers into its workspace and the host arrays that travel with them
+// (alive until the stream has been synchronised): what the point stage leaves to HoughLinesP's second stage, whichever kernel runs it.
+struct PphtPass {
+    uint8_t* d_mask = nullptr; size_t mask_page = 0;                // byte masks (k_dark_mask)
+    unsigned* d_nz = nullptr; unsigned long long* d_nzoff = nullptr; unsigned* d_count = nullptr;   // point list, a page's start, its points
+    const unsigned long long* h_nzoff = nullptr; const unsigned* h_count = nullptr;
+    float* d_ttab = nullptr; const float* h_ttab = nullptr;         // kNumAngle x {cos, sin}
+    int* d_lines = nullptr; unsigned long long* d_lnoff = nullptr; unsigned* d_cap = nullptr; unsigned* d_nlines = nullptr;   // segment list, a page's start, its room, segments found
+    const unsigned long long* h_lnoff = nullptr; const unsigned* h_cap = nullptr;
+};
+// ppht_group.hip: HoughLinesP's second stage with the accumulator in LDS, a group of workgroups per page.
 struct PphtGroupIn {
     int n_pages = 0, width = 0, height = 0, threshold = 0, line_length = 0, line_gap = 0;
-    const uint8_t* d_mask = nullptr; size_t mask_page = 0;          // byte masks (k_dark_mask)
-    const unsigned* d_nz = nullptr; const unsigned long long* d_nzoff = nullptr; const unsigned* d_count = nullptr;
-    const float* d_ttab = nullptr; const float* h_ttab = nullptr;
-    int* d_lines = nullptr; const unsigned long long* d_lnoff = nullptr; const unsigned* d_cap = nullptr; unsigned* d_nlines = nullptr;
-    const unsigned* h_count = nullptr; const unsigned long long* h_nzoff = nullptr;
+    PphtPass pass;
     std::vector<int> page_list;          // pages to process, heaviest first
     int cu_limit = 0;                    // workgroups at most (0: one per CU)
     hipEvent_t ev[2] = {nullptr, nullptr};   // optional: recorded before / after the group kernel (diagnostics)

@@ -6,7 +6,7 @@
 //                    and cv::invert's closed form for 3 x 3, all in float64 with one rounding per written operation
 //   k_warp_persp     warpPerspectiveInvoker + remapBilinear: per pixel (X0 + M[0] x1) * (32 / (W0 + M[6] x1)) in float64, rounded
 //                    half to even to 5-bit fixed point, four taps weighted 32 (32 - fx)(32 - fy) ..., (sum + 2^14) >> 15.  The
-//                    shape is k_warp's (deskew.hip): a workgroup makes 256 consecutive pixels of kPerspRows output rows, the bytes
+//                    shape is k_warp's (rotate.hip): a workgroup makes 256 consecutive pixels of kPerspRows output rows, the bytes
 //                    leave through LDS as aligned dwords, and both taps of a source row come with one 8-byte load where all four
 //                    taps are inside the page.  OpenCV walks the output in blocks of bw columns and forms X0 / Y0 / W0 at the
 //                    block's first column: the block width is part of the arithmetic (M[0] x is not M[0] xb + M[0] x1 in floating
@@ -38,7 +38,7 @@ constexpr int kPerspRows = 4;
 constexpr int kPerspBlocks = 5;
 constexpr int kMaxSide = 32767;
 
-// 8 bytes at any alignment (global memory takes unaligned dword accesses on gfx9+); as in deskew.hip
+// 8 bytes at any alignment (global memory takes unaligned dword accesses on gfx9+); as in rotate.hip
 __device__ __forceinline__ uint2 load8u(const uint8_t* p)
 {
     uint2 v;

@@ -8,6 +8,8 @@
 //   group size the G returned is the smallest >= min_g whose largest member fits the budget - recomputed here from corner
 //              projections in long double, not from the plan's own rows - and the values of five page sizes worked out beforehand;
 //   refusals   no plan for a side of 8001 or a threshold of 0.
+// And the workspace of a pass of the search, from figures worked out by hand: the fixed blocks (aligned, in order, without gap
+// or overlap, the total), the two lists from given counts, the pages a pass takes under a budget.
 // Built by tests/cpp/Makefile (g++), no device.
 #include <cfenv>
 #include <cmath>
@@ -148,6 +150,58 @@ static void check_size(int W, int H)
 
 static int plan_g(int W, int H, int thr = 100, int min_g = 1) { return plan_group(W, H, thr, ttab, kBudget, min_g).G; }
 
+static size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// The fixed workspace of a pass: the blocks in the driver's order, 256-aligned, each with room for what it holds and ending
+// where the next one starts; the total is the sum the driver formed before the layout existed: hist + thr + 2 rows +
+// 4 per-page words + 2 per-page offsets + trig table + masks, each rounded to 256.
+static void check_fixed(int n, int W, int H, size_t want_total)
+{
+    const PphtFixed f = ppht_fixed(n, W, H);
+    const size_t N = (size_t)n, mask_page = up256((size_t)W * H);
+    const size_t off[13] = {f.hist, f.thr, f.row_count, f.row_off, f.count, f.n_lines, f.cap, f.nz_off, f.lines_off, f.ttab,
+                            f.page_list, f.mask, f.total};
+    const size_t need[12] = {N * 1024, N * 4, N * H * 4, N * H * 4, N * 4, N * 4, N * 4, N * 8, N * 8, 1440, N * 4, N * mask_page};
+    CHECK(f.hist == 0 && f.mask_page == mask_page);
+    for (int b = 0; b < 12; ++b) CHECK(off[b] % 256 == 0 && off[b + 1] == off[b] + up256(need[b]));
+    const size_t total = up256(N * 1024) + up256(N * 4) + 2 * up256(N * H * 4) + 4 * up256(N * 4) + 2 * up256(N * 8) + up256(1440) + N * mask_page;
+    CHECK(f.total == total && f.total == want_total);
+}
+
+static void check_layout()
+{
+    check_fixed(3, 300, 390, 367872);   // 3072 + 256 + 2 * 4864 + 4 * 256 + 2 * 256 + 1536 + 3 * 117248
+    check_fixed(1, 1, 1, 5120);         // 1024 + 256 + 2 * 256 + 4 * 256 + 2 * 256 + 1536 + 256: no block below 256 bytes
+    check_fixed(5, 203, 97, 111104);    // rows of 5 * 97 * 4 = 1940 -> 2048 bytes, masks of 19691 -> 19712: 5120 + 256 + 2 * 2048 + 4 * 256 + 2 * 256 + 1536 + 5 * 19712
+    {   // the lists of five pages at findAngle's parameters for a page 896 wide: a segment per 112 / 21 = 5 points
+        const unsigned count[5] = {0, 1, 64, 65, 1000};
+        const PphtLists l = ppht_lists(count, 5, 112, 20);
+        const unsigned long long nz_off[5] = {0, 0, 64, 128, 256}, ln_off[5] = {0, 16, 32, 60, 89};
+        const unsigned cap[5] = {16, 16, 28, 29, 216};
+        for (int i = 0; i < 5; ++i) CHECK(l.nz_off[(size_t)i] == nz_off[i] && l.cap[(size_t)i] == cap[i] && l.lines_off[(size_t)i] == ln_off[i]);
+        CHECK(l.nz_total == 1280 && l.lines_total == 305);
+        CHECK(l.nz_bytes == 5376 && l.lines_bytes == 5376);   // r256(4 * 1280 + 256), r256(16 * 305 + 256)
+        // a line no longer than the gap + 1 may end after every point: line_length 37 / (line_gap 37 + 1) = 0 -> 1
+        const PphtLists m = ppht_lists(count, 5, 37, 37), g0 = ppht_lists(count, 5, 37, 20);
+        for (int i = 0; i < 5; ++i) CHECK(m.cap[(size_t)i] == count[i] + 16 && g0.cap[(size_t)i] == count[i] + 16);
+        CHECK(ppht_lists(count, 0, 112, 20).nz_bytes == 256 && ppht_lists(count, 0, 112, 20).lines_bytes == 256);
+    }
+    // pages per pass: max(1, min(n, 16384, budget / per_page)) with the per-page cost written out
+    CHECK(ppht_bytes_per_page(300, 390) == 1292484);   // 2 * 117248 + 180 * 1381 * 4 + 390 * 8 + 2048 + 58500
+    static const int ns[] = {0, 1, 2, 3, 255, 16384, 16385, 100000};
+    static const int wh[][2] = {{1, 1}, {300, 390}, {203, 97}, {2480, 3508}, {32767, 16}};
+    static const size_t budgets[] = {0, 1, (size_t)1 << 20, 1292483, 1292484, 2 * 1292484 - 1, (size_t)1 << 30, (size_t)24576 << 20, (size_t)1 << 46};
+    for (int n : ns)
+        for (const auto& s : wh)
+            for (size_t budget : budgets) {
+                const size_t W = (size_t)s[0], H = (size_t)s[1];
+                const size_t per = 2 * up256(W * H) + 180 * ((W + H) * 2 + 1) * 4 + H * 8 + 2048 + W * H / 2;
+                const size_t want = std::max<size_t>(1, std::min<size_t>({(size_t)n, (size_t)16384, budget / per}));
+                CHECK((size_t)ppht_pages_per_pass(n, s[0], s[1], budget) == want);
+            }
+    CHECK(ppht_pages_per_pass(3, 300, 390, (size_t)1 << 20) == 1 && ppht_pages_per_pass(100000, 1, 1, (size_t)1 << 46) == 16384);
+}
+
 int main()
 {
     CHECK(std::fegetround() == FE_TONEAREST);
@@ -192,6 +246,7 @@ int main()
     {   // a budget nothing fits
         CHECK(plan_group(8000, 8000, 100, ttab, 16 * 1024, 1).G == 0);
     }
+    check_layout();
     if (bad) { std::printf("ppht_plan: %d FAILED\n", bad); return 1; }
     std::printf("ppht_plan: OK\n");
     return 0;

@@ -100,8 +100,8 @@ def test_no_device_means_loud_failure_not_cpu_fallback(prl):
 
 
 def test_entry_statuses_without_a_device(prl):
-    """The *_host entries and the batch entries on the shared device workspace check their arguments in a fixed order before
-    they look for a device: one row per rejection class (a few with two faults pin which check comes first), then valid calls,
+    """The *_host entries, the batch entries on the shared device workspace and the deskew / rotate / find_angle / houghp entries
+    check their arguments in a fixed order before they look for a device: one row per rejection class (a few with two faults pin which check comes first), then valid calls,
     which fail with PRL_ERR_NO_DEVICE here (those rows are skipped where a device is visible).  No row reaches the buffers."""
     import torch
     from prlib_amd import _capi as E
@@ -112,6 +112,9 @@ def test_entry_statuses_without_a_device(prl):
     s, d = buf.ctypes.data, buf.ctypes.data + (1 << 15)
     angles = (C.c_double * 2)(1.0, -2.0)
     ang = C.addressof(angles)
+    wh, nseg = (C.c_int32 * 2)(0, 0), (C.c_int32 * 2)(0, 0)   # results of the deskew / find_angle entries: never the page buffer
+    whp = C.addressof(wh)
+    out_w, out_h, one_angle, one_nseg = C.c_int(0), C.c_int(0), C.c_double(0.0), C.c_int32(0)
     sauvola = prl.make_params(prl.SAUVOLA, 3)   # 12 x 8 page: 11 x 7 output, 14 x 10 padded
     even = prl.make_params(prl.SAUVOLA, 4)
     bad_method = prl.make_params(prl.SAUVOLA, 3)
@@ -185,6 +188,46 @@ def test_entry_statuses_without_a_device(prl):
             (dict(dst=None), ARG), (dict(dst=s), ARG), (dict(ss=11), ARG), (dict(w=32768, ss=32768), ARG), (dict(h=32768), ARG),
             (dict(n=0), OK), (dict(w=0, c=0), EMPTY), (dict(c=0, ang=None), CH), (dict(n=0, h=32768), ARG),
             (dict(), NODEV), (dict(c=4, ss=48, ds=48), NODEV), (dict(ds=1), NODEV)]),   # (dst_step: checked per chunk, after the device)
+        # deskew: a page's result may be max(w, h) wide, so that side bounds dst_step
+        (L.prl_hip_deskew_batch_device, dict(n=1, c=1, src=s, sps=ps, ss=12, w=12, h=8, dst=d, dps=ps, ds=12, wh=whp, ang=None,
+                                             stream=None), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(c=0), CH), (dict(c=2), CH), (dict(c=5), CH), (dict(n=-1), ARG),
+            (dict(src=None), ARG), (dict(dst=None), ARG), (dict(dst=s), ARG), (dict(wh=None), ARG), (dict(ss=11), ARG),
+            (dict(ds=11), ARG), (dict(w=8, h=12, ss=8, ds=11), ARG), (dict(h=32768, ds=32768), ARG),
+            (dict(w=32768, ss=32768, ds=32768), ARG), (dict(n=0), OK),
+            (dict(w=0, c=2), EMPTY), (dict(c=2, n=-1), CH), (dict(c=2, wh=None), CH), (dict(n=0, dst=None), ARG),
+            (dict(n=0, h=32768, ds=32768), ARG),
+            (dict(), NODEV), (dict(ang=ang), NODEV), (dict(c=3, ss=36, ds=36), NODEV), (dict(c=4, ss=48, ds=48), NODEV),
+            (dict(w=8, h=12, ss=8), NODEV), (dict(h=32767, ds=32767), NODEV)]),
+        # (dst_step of the two *_host entries below: compared with the result's width after the device stage; their sides are
+        # the device stage's to refuse)
+        (L.prl_hip_deskew_host, dict(c=1, src=s, ss=12, w=12, h=8, dst=d, ds=12, ow=C.byref(out_w), oh=C.byref(out_h), angle=None), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(src=None), EMPTY), (dict(c=0), CH), (dict(c=2), CH), (dict(c=5), CH),
+            (dict(dst=None), ARG), (dict(ow=None), ARG), (dict(oh=None), ARG), (dict(ss=11), ARG),
+            (dict(src=None, c=2), EMPTY), (dict(c=2, dst=None), CH),
+            (dict(), NODEV), (dict(ds=1), NODEV), (dict(angle=C.byref(one_angle)), NODEV), (dict(c=3, ss=36, ds=36), NODEV),
+            (dict(c=4, ss=48, ds=48), NODEV), (dict(h=32768), NODEV)]),
+        (L.prl_hip_rotate_host, dict(c=1, angle=3.0, src=s, ss=12, w=12, h=8, dst=d, ds=12), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(src=None), EMPTY), (dict(c=0), CH), (dict(c=5), CH),
+            (dict(dst=None), ARG), (dict(ss=11), ARG), (dict(c=3, ss=35), ARG),
+            (dict(src=None, c=0), EMPTY), (dict(c=0, dst=None), CH),
+            (dict(), NODEV), (dict(ds=1), NODEV), (dict(angle=90.0), NODEV), (dict(c=2, ss=24, ds=24), NODEV),
+            (dict(c=4, ss=48, ds=48), NODEV), (dict(h=32768), NODEV)]),
+        (L.prl_hip_find_angle_batch_device, dict(n=1, src=s, sps=ps, ss=12, w=12, h=8, ang=ang, nseg=None, stream=None), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(n=-1), ARG), (dict(src=None), ARG), (dict(ang=None), ARG),
+            (dict(ss=11), ARG), (dict(h=32768), ARG), (dict(w=32768, ss=32768), ARG), (dict(n=0), OK),
+            (dict(w=0, n=-1), EMPTY), (dict(w=0, src=None), EMPTY), (dict(n=0, ang=None), ARG), (dict(n=0, h=32768), ARG),
+            (dict(), NODEV), (dict(nseg=C.addressof(nseg)), NODEV), (dict(h=32767), NODEV)]),
+        (L.prl_hip_find_angle_host, dict(src=s, ss=12, w=12, h=8, ang=C.byref(one_angle), nseg=None), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(src=None), EMPTY), (dict(ang=None), ARG), (dict(ss=11), ARG),
+            (dict(h=32768), ARG), (dict(w=32768, ss=32768), ARG), (dict(src=None, ang=None), EMPTY), (dict(w=0, ss=0, ang=None), EMPTY),
+            (dict(), NODEV), (dict(nseg=C.byref(one_nseg)), NODEV), (dict(h=32767), NODEV)]),
+        (L.prl_hip_houghp_device, dict(src=s, ss=12, w=12, h=8, thr=10, ll=5, gap=2, lines=d, cap=4, nl=C.byref(out_w), stream=None), [
+            (dict(w=0), EMPTY), (dict(h=0), EMPTY), (dict(src=None), ARG), (dict(nl=None), ARG), (dict(lines=None), ARG),
+            (dict(ss=11), ARG), (dict(h=32768), ARG), (dict(w=32768, ss=32768), ARG),
+            (dict(w=0, src=None), EMPTY), (dict(h=0, nl=None), EMPTY),
+            (dict(), NODEV), (dict(lines=None, cap=0), NODEV), (dict(lines=None, cap=-1), NODEV), (dict(thr=0, ll=0, gap=-1), NODEV),
+            (dict(h=32767), NODEV)]),
     ]
     wrong = []
     for fn, args, cases in table:

@@ -176,6 +176,60 @@ def test_group_that_gives_up_is_redone_in_the_same_call():
     assert left and max(left) >= 1, err[-2000:]
 
 
+_CHILD_PASSES = r'''
+import numpy as np, torch, sys
+sys.path.insert(0, %r)
+import prlib_amd
+from prlib_amd import synth
+from oracle import capi as oc
+def mark(name):
+    sys.stderr.flush(); print("== " + name, file=sys.stderr, flush=True)
+bad = []
+pages = np.stack([synth.text_page_numpy(390, 300, 20 + i, skew_deg=s) for i, s in enumerate((2.5, -4.0, 0.0))])
+mark("deskew")
+outs, angles = prlib_amd.deskew(torch.from_numpy(pages).cuda())
+for i in range(3):
+    want, info = oc.deskew(pages[i])
+    got = outs[i].cpu().numpy()
+    if angles[i] != info["angle"] or got.shape != want.shape or not np.array_equal(got, want):
+        bad.append(("deskew", i, float(angles[i]), info["angle"]))
+binary = np.stack([oc.otsu(p)[1] for p in pages])
+t = torch.from_numpy(binary).cuda()
+mark("find_angle")
+ang, nseg = prlib_amd.findAngle(t, return_segments=True)
+mark("alone")
+for i in range(3):
+    a1, n1 = prlib_amd.findAngle(t[i], return_segments=True)
+    if (float(ang[i]), int(nseg[i])) != (a1, n1) or float(ang[i]) != oc.find_angle(binary[i])[0]:
+        bad.append(("find_angle", i, float(ang[i]), int(nseg[i]), a1, n1, oc.find_angle(binary[i])))
+print("BAD", len(bad), bad)
+'''
+
+
+def test_standalone_entries_at_one_page_per_pass():
+    """prl_hip_deskew_batch_device and prl_hip_find_angle_batch_device over several passes: with a work budget of 1 MiB
+    (PRL_HIP_DESKEW_WORK_MB, read once per process by the product library, hence the child) a 300 x 390 page, which costs
+    1 292 484 bytes of it, is a pass of its own, so pages 1 and 2 run the second- and third-pass offsets of out_wh, angles and
+    the page sets.  Per page: deskew gives the oracle's angle and bytes; find_angle gives what the page gives alone, and the
+    oracle's angle.  The debug lines show that every entry did take three passes of one page."""
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PRL_HIP_DEBUG="1", PRL_HIP_DESKEW_WORK_MB="1")
+    r = subprocess.run([sys.executable, "-c", _CHILD_PASSES % root], capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0 and "BAD 0 " in r.stdout, r.stdout + r.stderr[-3000:]
+    section, one_page_passes = None, {"deskew": 0, "find_angle": 0, "alone": 0}
+    for ln in r.stderr.splitlines():
+        if ln.startswith("== "):
+            section = ln[3:]
+        elif section and "group kernel: 1 pages" in ln:
+            one_page_passes[section] += 1
+        assert "group kernel: 2 pages" not in ln and "group kernel: 3 pages" not in ln, ln
+    assert one_page_passes["deskew"] >= 3 and one_page_passes["find_angle"] >= 3, (one_page_passes, r.stderr[-3000:])
+
+
 def test_deskew_argument_errors(prl, cuda_device):
     import torch
 

@@ -1,4 +1,4 @@
-"""HoughLinesP's three kernels (k_ppht_group of ppht_group.hip; k_ppht_mw and k_ppht of deskew.hip) against the CPU oracle on the
+"""HoughLinesP's three kernels (k_ppht_group of ppht_group.hip; k_ppht_mw and k_ppht of ppht.hip) against the CPU oracle on the
 shared case list (tests/houghp_cases.py): every group size the plan can give, the page and point-count edges, several pages per
 group, the placement by XCD, the eligibility edges, a segment list smaller than the result, a strided view.  All comparisons are
 exact: same segments, same order.

@@ -8,7 +8,7 @@ C   64 x A4 x 3 channels, the same quad
 
 Per workload, timed in the same run between two device events on the current stream:
     warp_crop   prl_hip_warp_crop_batch_device (sizes, matrices, the record upload and k_warp_persp)
-    rotate      prl_hip_rotate_batch_device by 3.7 degrees on the same pages (k_warp of deskew.hip: the affine yardstick; its result
+    rotate      prl_hip_rotate_batch_device by 3.7 degrees on the same pages (k_warp of rotate.hip: the affine yardstick; its result
                 is the max(W, H) square, so it makes more pixels - compare ns_per_out_px)
     copy        a device-to-device copy of the batch (the streaming yardstick)
 ms: per repeat the median of `steps` calls after `warmup`; the line reports the median, the minimum and the maximum of the
