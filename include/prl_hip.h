@@ -615,6 +615,67 @@ int prl_hip_cooccurrence_batch_device(int n_pages, int border, int min_diff, con
  */
 int prl_hip_mokji_threshold(const uint32_t cooc[256 * 256], int min_edge_magnitude, int* threshold);
 
+/* ---- focus measures: the blur detection of src/detectors/blurDetection.cpp (LAPM, LAPV, TENG, GLVN) ------------------------- */
+
+#define PRL_FOCUS_SUM_P 0       /* sum of p */
+#define PRL_FOCUS_SUM_P2 1      /* sum of p^2 */
+#define PRL_FOCUS_SUM_LAP 2     /* sum of L */
+#define PRL_FOCUS_SUM_LAP2 3    /* sum of L^2 */
+#define PRL_FOCUS_SUM_LAPM4 4   /* sum of |X| + |Y| */
+#define PRL_FOCUS_SUM_TENG 5    /* sum of Gx^2 + Gy^2 */
+#define PRL_FOCUS_LAPM 0
+#define PRL_FOCUS_LAPV 1
+#define PRL_FOCUS_TENG 2
+#define PRL_FOCUS_GLVN 3
+
+/*
+ * The four focus measures of the reference (blurDetection.cpp:32-83; its prl::isBlurred returns false and calls none of them) on
+ * 8-bit pages of 1, 3 or 4 interleaved channels: one read-only pass (focus.hip) leaves six integer sums per page AND channel, and
+ * the measures follow from the sums on the host in float64.  Write p(y, x) for one channel of one page and N = width * height.
+ * Neighbours outside the page are BORDER_REFLECT_101 (cv::borderInterpolate: index -1 -> 1, n -> n - 2, a side of length 1 maps
+ * everything to 0).  Every sum runs over all N pixels, in int64:
+ *   [0] S_P = sum p;  [1] S_P2 = sum p^2;
+ *   [2] S_LAP = sum L, L = p(y-1, x) + p(y+1, x) + p(y, x-1) + p(y, x+1) - 4 p(y, x): cv::Laplacian(src, CV_64F), ksize 1 (:53);
+ *   [3] S_LAP2 = sum L^2;
+ *   [4] S_LAPM4 = sum (|X| + |Y|), X = the (-1, 2, -1) filter along x of the rows y-1, y, y+1 weighted (1, 2, 1), Y the same with
+ *       the axes exchanged: four times Lx, Ly of :34-41 (cv::getGaussianKernel(3, -1) is exactly (1/4, 1/2, 1/4));
+ *   [5] S_TENG = sum (Gx^2 + Gy^2), Gx, Gy = cv::Sobel(..., teng_ksize), unnormalised: (-1, 0, 1) along the axis and, for
+ *       teng_ksize == 3, (1, 2, 1) across it; teng_ksize == 1: (-1, 0, 1) alone.  Other sizes and the Scharr kernel are
+ *       PRL_ERR_BAD_ARG (from 5 on a sum can pass 2^53 on a large page, where the order of OpenCV's double sum would show).
+ * Bounds: |L| <= 1020, |X|, |Y| <= 2040, Gx^2 + Gy^2 <= 2 * 1020^2; on a 32768 x 32768 page the largest sum is 2.3e15 < 2^53, so
+ * every intermediate of the reference (an integer or a multiple of 1/4) and every sum is exact in float64 in any order.
+ * The measures of a channel from its sums, float64, one rounding per written operation, scale = 1.0 / N (cv::mean and
+ * cv::meanStdDev as sum * scale [upstream, generic path]: the canonical choice, parity unpinned as in DESIGN.md §2):
+ *   [0] LAPM = (S_LAPM4 / 4.0) * scale
+ *   [1] LAPV: m = S_LAP * scale; sd = sqrt(max(S_LAP2 * scale - m * m, 0.0)); sd * sd
+ *   [2] TENG = S_TENG * scale
+ *   [3] GLVN: mu = S_P * scale; sg = sqrt(max(S_P2 * scale - mu * mu, 0.0)); (sg * sg) / mu  (an all-zero page: NaN, as 0 / 0 is
+ *       in the reference)
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_ARG (teng_ksize other
+ * than 1 and 3); PRL_ERR_BAD_CHANNELS (channels other than 1, 3, 4); PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row
+ * bytes, width or height above 32768).  n_pages == 0 is PRL_OK.
+ */
+
+/*
+ * d_sums[page][channel][6] (device memory, int64) = the six sums; the call overwrites it.  Pages and rows may be strided.  Enqueues
+ * on `stream` and does not synchronise; d_src is never written; no workspace.  The workgroups' partial sums meet in d_sums by
+ * 64-bit integer atomics: the result does not depend on their order.
+ */
+int prl_hip_focus_sums_batch_device(int n_pages, int channels, int teng_ksize, const uint8_t* d_src, size_t src_page_stride,
+                                    size_t src_step, int width, int height, int64_t* d_sums, void* stream);
+
+/*
+ * One page in host memory: measures[channel][4]; sums (optional, may be null) receives [channel][6].  Same checks (no page count).
+ */
+int prl_hip_focus_measures_host(int channels, int teng_ksize, const uint8_t* src, size_t src_step, int width, int height,
+                                double* measures, int64_t* sums);
+
+/*
+ * The four measures of one channel from its six sums, no device needed.  PRL_ERR_EMPTY for width or height <= 0; PRL_ERR_BAD_ARG
+ * for a null pointer or a side above 32768.
+ */
+int prl_hip_focus_from_sums(const int64_t sums[6], int width, int height, double measures[4]);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

@@ -78,6 +78,7 @@ EXPORTED_SYMBOLS = [
     "prl_hip_hough_lines_geometry", "prl_hip_hough_accumulator_batch_device", "prl_hip_hough_lines_batch_device", "prl_hip_hough_lines_host",
     "prl_hip_hough_edges_batch_device", "prl_hip_hough_edges_host", "prl_hip_hough_line_quad",
     "prl_hip_hough_line_contour_batch_device", "prl_hip_hough_line_contour_host",
+    "prl_hip_focus_sums_batch_device", "prl_hip_focus_measures_host", "prl_hip_focus_from_sums",
 ]
 
 
@@ -273,6 +274,9 @@ def lib() -> C.CDLL:
         L.prl_hip_hough_line_quad.argtypes = [vp, i, i, i, vp, P(C.c_int)]
         L.prl_hip_hough_line_contour_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, vp, vp, vp]
         L.prl_hip_hough_line_contour_host.argtypes = [i, vp, sz, i, i, vp, vp, vp]
+        L.prl_hip_focus_sums_batch_device.argtypes = [i, i, i, vp, sz, sz, i, i, vp, vp]
+        L.prl_hip_focus_measures_host.argtypes = [i, i, vp, sz, i, i, vp, vp]
+        L.prl_hip_focus_from_sums.argtypes = [vp, i, i, vp]
         _lib = L
     return _lib
 

@@ -20,6 +20,7 @@
 //   src/balance/balanceGrayWorldWhite.h:33                 prl::grayWorldWhiteBalance
 //   src/cleanBackgroundToWhite.h:40                        prl::cleanBackgroundToWhite
 //   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
+//   src/detectors/blurDetection.h:35                       prl::isBlurred (+ prl::focusMeasures)
 //   src/warp.h:49-73                                       prl::warpCrop
 //   src/border_detection/autoCrop.h:42-53                  prl::documentContour, prl::autoCrop
 //   src/border_detection/houghLine.h                       prl::findHoughLineContour
@@ -147,6 +148,20 @@ CV_EXPORTS void cleanBackgroundToWhite(const cv::Mat& inputImage, cv::Mat& outpu
 // above 127 on a page with an interior is StsBadArg.  On every error outputImage stays untouched.  The output is a new continuous
 // Mat; the input's pixels are never written (out may be in, or a view of it).
 CV_EXPORTS void binarizeMokji(const cv::Mat& inputImage, cv::Mat& outputImage, size_t maxEdgeWidth = 3, size_t minEdgeMagnitude = 20);
+
+// src/detectors/blurDetection.h:35 - returns false without looking at the image, as blurDetection.cpp:85-89 does: the reference
+// has no threshold for its four focus measures (LAPM_Algo, LAPV_Algo, TENG_Algo, GLVN_Algo, :32-83) and calls none of them.
+CV_EXPORTS bool isBlurred(const cv::Mat& inputImage);
+
+// An extension, not in the reference's header: those four measures of CHANNEL 0 of an 8-bit image of 1, 3 or 4 channels, as
+// cv::mean(FM).val[0] and mu.val[0] give them there (focus.hip; the arithmetic is stated in prl_hip.h, "focus measures").
+// tengKernelSize is cv::Sobel's ksize, 3 or 1.  std::invalid_argument for an empty image; cv::Exception StsUnsupportedFormat for a
+// depth other than CV_8U or channels other than 1, 3, 4; StsBadArg for another tengKernelSize or a side above 32768.  An
+// all-zero image has glvn NaN.  The input's pixels are never written.
+struct FocusMeasures {
+    double lapm, lapv, teng, glvn;
+};
+CV_EXPORTS FocusMeasures focusMeasures(const cv::Mat& inputImage, int tengKernelSize = 3);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

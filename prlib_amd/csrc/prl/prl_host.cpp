@@ -294,6 +294,26 @@ void prl::binarizeMokji(const cv::Mat& inputImage, cv::Mat& outputImage, size_t 
     outputImage = result;
 }
 
+// blurDetection.cpp:85-89: "TODO: find constants for blurring check for every algorithm", return false
+bool prl::isBlurred(const cv::Mat&)
+{
+    return false;
+}
+
+// blurDetection.cpp:32-83, channel 0 (cv::mean(FM).val[0], sigma.val[0], mu.val[0])
+prl::FocusMeasures prl::focusMeasures(const cv::Mat& inputImage, int tengKernelSize)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image for focus measures is empty");
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::focusMeasures: 8-bit images only");
+    const int cn = inputImage.channels();
+    if (cn != 1 && cn != 3 && cn != 4) raise(PRL_ERR_BAD_CHANNELS);
+    double m[4 * 4];
+    const int st = prl_hip_focus_measures_host(cn, tengKernelSize, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows, m,
+                                               nullptr);
+    if (st != PRL_OK) raise(st);
+    return prl::FocusMeasures{m[PRL_FOCUS_LAPM], m[PRL_FOCUS_LAPV], m[PRL_FOCUS_TENG], m[PRL_FOCUS_GLVN]};
+}
+
 namespace {
 
 constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255
