@@ -676,6 +676,79 @@ int prl_hip_focus_measures_host(int channels, int teng_ksize, const uint8_t* src
  */
 int prl_hip_focus_from_sums(const int64_t sums[6], int width, int height, double measures[4]);
 
+/* ---- basicDeblur: the float32 cv::GaussianBlur of 8-bit pages and the unsharp mask of src/deblur/basicDeblur.cpp:33-70 ------- */
+
+#define PRL_GAUSS_MAX_SIDE 255   /* the largest kernel side; above it PRL_ERR_BAD_WINDOW */
+
+/*
+ * prl::basicDeblur(in, out, gaussianKernelSize = 0, sigmaX = 9.0, sigmaY = 0.0, imageWeight = 0.75) on 8-bit pages of 1 to 4
+ * interleaved channels.  For every channel, with p the byte of a sample:
+ *   1. x = (float)p
+ *   2. g = cv::GaussianBlur(x, Size(k, k), sigmaX, sigmaY) in float32, BORDER_REFLECT_101
+ *   3. t = (x * alpha + g * beta) + 0.0f, alpha = (float)(2 * imageWeight), beta = (float)(2 * imageWeight - 2) (each computed in
+ *      float64 and rounded once): cv::addWeighted on CV_32F
+ *   4. out = saturate_u8(cvRound(t)): half to even; NaN, +-inf and what lies outside int32 give 0
+ * One fused kernel (deblur.hip) does the four steps; its only global write is the destination byte.  The rules of step 2, as
+ * cv::GaussianBlur has them for a depth that is not 8-bit (gauss.h states them in C++, tests/deblur_ref.py in numpy):
+ *   sigmaY            sigmaY <= 0 -> sigmaY = sigmaX.
+ *   derived side      a side k <= 0 with its sigma > 0 is cvRound(sigma * 4 * 2 + 1) | 1, per axis (the factor is 4, not 3: the depth
+ *                     is not 8-bit): k = 0, sigmaX = 9 gives 73 x 73; k = 0, sigmaX = 1, sigmaY = 3 gives 9 x 25.
+ *   valid side        after that step a side must be positive and odd, and here at most PRL_GAUSS_MAX_SIDE.
+ *   weights           cv::getGaussianKernel(n, max(sigma, 0), CV_32F): the fixed tables for n = 1, 3, 5, 7 ({1}, {1/4, 1/2, 1/4},
+ *                     {1/16, 1/4, 3/8, 1/4, 1/16}, {1/32, 7/64, 7/32, 9/32, ...}) apply only when sigma <= 0; otherwise
+ *                     s = sigma > 0 ? sigma : ((n - 1) * 0.5 - 1) * 0.3 + 0.8, t_i = exp(-0.5 / (s * s) * x_i * x_i) with
+ *                     x_i = i - (n - 1) * 0.5 in float64, the sum in index order, w_i = (float)(t_i * (1 / sum)).
+ *   shared weights    ky is kx when the sides are equal and |sigmaX - sigmaY| < DBL_EPSILON; else ky is made from its own side and sigma.
+ *   1 x 1             a copy: g = x (the only weight is 1.0f).
+ *   thin pages        a page of one row or one column gets no special case (the default border type carries no BORDER_ISOLATED):
+ *                     it is filtered through its reflections.
+ *   border            cv::borderInterpolate(i, len, BORDER_REFLECT_101) with its loop: -1 -> 1, len -> len - 2; a page narrower
+ *                     than the radius reflects more than once; len == 1 gives index 0.
+ *   operation order   row pass with n >= 7 (and n == 1): w_0 x_0, then + w_k x_k for k ascending; row pass with n = 3 or 5: the centre
+ *                     x_r w_r, then + (x_(r+k) + x_(r-k)) w_(r+k) for k = 1 .. r; column pass: the centre w_r v_r, then
+ *                     + w_(r+k) (v_(r+k) + v_(r-k)) outward.  Every product and every sum is one float32 rounding, never contracted:
+ *                     the order DESIGN.md §4.4c pins for ADAPTIVE_THRESH_GAUSSIAN_C.  Parity with an OpenCV build is unpinned (§2).
+ * On interleaved pages the row pass is a 1-D filter over samples with tap stride `channels`, reflected on the pixel index.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_WINDOW (a kernel size
+ * that does not fit an int; a side <= 0 whose sigma is not > 0, a NaN included; an even side; a side, given or derived, above
+ * PRL_GAUSS_MAX_SIDE); PRL_ERR_BAD_ARG (channels outside 1..4; a NaN or infinite sigma or weight; a null pointer; negative n_pages;
+ * a step below the row bytes; a float destination or a step of it that is no multiple of 4; width or height above 32768; source
+ * and destination sharing a byte: in place is not allowed, every output reads its neighbours' inputs).  n_pages == 0 is PRL_OK.
+ * Not built: sides above PRL_GAUSS_MAX_SIDE, depths other than 8-bit, and the reference's wienerFilter (a DFT).
+ */
+
+/*
+ * n pages per call; pages and rows may be strided.  Enqueues on `stream` and does not synchronise; needs no workspace; d_src is
+ * never written.  kernel_size is the reference's size_t (both sides); a value <= 0 derives the sides from the sigmas.
+ */
+int prl_hip_basic_deblur_batch_device(int n_pages, int channels, long long kernel_size, double sigma_x, double sigma_y,
+                                      double image_weight, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                      int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+/* One page in host memory, through the staging area.  Same checks (no page count; the two may not overlap either). */
+int prl_hip_basic_deblur_host(int channels, long long kernel_size, double sigma_x, double sigma_y, double image_weight,
+                              const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+
+/*
+ * Step 2 alone, the float32 cv::GaussianBlur(Size(kernel_w, kernel_h), sigma_x, sigma_y) of 8-bit pages: the same kernel writing g
+ * instead of the byte.  d_dst holds float32 samples, width * channels a row; dst_page_stride and dst_step are in BYTES and, like
+ * d_dst, multiples of 4.  The same checks in the same order.
+ */
+int prl_hip_gaussian_blur_f32_batch_device(int n_pages, int channels, long long kernel_w, long long kernel_h, double sigma_x,
+                                           double sigma_y, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                           int height, float* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_gaussian_blur_f32_host(int channels, long long kernel_w, long long kernel_h, double sigma_x, double sigma_y,
+                                   const uint8_t* src, size_t src_step, int width, int height, float* dst, size_t dst_step);
+
+/*
+ * The rules on the host, no device needed.  prl_hip_gaussian_blur_size: the sides cv::GaussianBlur(Size(kernel_w, kernel_h),
+ * sigma_x, sigma_y) filters with (sigma_y <= 0 -> sigma_x, the derived side); PRL_ERR_BAD_WINDOW as above, PRL_ERR_BAD_ARG for a
+ * null pointer or a NaN or infinite sigma.  prl_hip_gaussian_kernel_f32: the n weights of cv::getGaussianKernel(n, sigma, CV_32F)
+ * (sigma <= 0: the tables up to 7, else the sigma derived from n); PRL_ERR_BAD_WINDOW for n <= 0, even or above PRL_GAUSS_MAX_SIDE,
+ * PRL_ERR_BAD_ARG for a null pointer or a NaN or infinite sigma.
+ */
+int prl_hip_gaussian_blur_size(long long kernel_w, long long kernel_h, double sigma_x, double sigma_y, int* out_w, int* out_h);
+int prl_hip_gaussian_kernel_f32(int n, double sigma, float* w);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

@@ -79,6 +79,8 @@ EXPORTED_SYMBOLS = [
     "prl_hip_hough_edges_batch_device", "prl_hip_hough_edges_host", "prl_hip_hough_line_quad",
     "prl_hip_hough_line_contour_batch_device", "prl_hip_hough_line_contour_host",
     "prl_hip_focus_sums_batch_device", "prl_hip_focus_measures_host", "prl_hip_focus_from_sums",
+    "prl_hip_basic_deblur_batch_device", "prl_hip_basic_deblur_host", "prl_hip_gaussian_blur_f32_batch_device",
+    "prl_hip_gaussian_blur_f32_host", "prl_hip_gaussian_blur_size", "prl_hip_gaussian_kernel_f32",
 ]
 
 
@@ -277,6 +279,13 @@ def lib() -> C.CDLL:
         L.prl_hip_focus_sums_batch_device.argtypes = [i, i, i, vp, sz, sz, i, i, vp, vp]
         L.prl_hip_focus_measures_host.argtypes = [i, i, vp, sz, i, i, vp, vp]
         L.prl_hip_focus_from_sums.argtypes = [vp, i, i, vp]
+        ll = C.c_longlong
+        L.prl_hip_basic_deblur_batch_device.argtypes = [i, i, ll, d, d, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_basic_deblur_host.argtypes = [i, ll, d, d, d, vp, sz, i, i, vp, sz]
+        L.prl_hip_gaussian_blur_f32_batch_device.argtypes = [i, i, ll, ll, d, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_gaussian_blur_f32_host.argtypes = [i, ll, ll, d, d, vp, sz, i, i, vp, sz]
+        L.prl_hip_gaussian_blur_size.argtypes = [ll, ll, d, d, P(C.c_int), P(C.c_int)]
+        L.prl_hip_gaussian_kernel_f32.argtypes = [i, d, vp]
         _lib = L
     return _lib
 

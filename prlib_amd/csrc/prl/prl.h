@@ -21,6 +21,7 @@
 //   src/cleanBackgroundToWhite.h:40                        prl::cleanBackgroundToWhite
 //   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
 //   src/detectors/blurDetection.h:35                       prl::isBlurred (+ prl::focusMeasures)
+//   src/deblur/basicDeblur.h:32-34                         prl::basicDeblur
 //   src/warp.h:49-73                                       prl::warpCrop
 //   src/border_detection/autoCrop.h:42-53                  prl::documentContour, prl::autoCrop
 //   src/border_detection/houghLine.h                       prl::findHoughLineContour
@@ -162,6 +163,16 @@ struct FocusMeasures {
     double lapm, lapv, teng, glvn;
 };
 CV_EXPORTS FocusMeasures focusMeasures(const cv::Mat& inputImage, int tengKernelSize = 3);
+
+// src/deblur/basicDeblur.h:32-34 - the unsharp mask of basicDeblur.cpp:33-70 on every channel of an 8-bit image of 1 to 4 channels:
+// out = saturate_u8(cvRound(x * (float)(2 w) + GaussianBlur_f32(x) * (float)(2 w - 2))) (deblur.hip; the rules are stated in
+// prl_hip.h, "basicDeblur").  std::invalid_argument("Input image for deblurring is empty") for an empty image; cv::Exception
+// StsAssert where cv::GaussianBlur's CV_Assert on the kernel size fails (an even size, or size 0 without a positive sigma);
+// StsNotImplemented for a depth other than CV_8U; StsUnsupportedFormat for more than 4 channels; StsBadArg for a kernel side above
+// 255, a size beyond int, a NaN or infinite sigma or weight, an image side above 32768 (documented deviations).  outputImage may be
+// inputImage: the result is a new Mat, and the input's pixels are never written.
+CV_EXPORTS void basicDeblur(const cv::Mat& inputImage, cv::Mat& outputImage, const size_t gaussianKernelSize = 0, const double sigmaX = 9.0,
+                            const double sigmaY = 0.0, const double imageWeight = 0.75);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

@@ -314,6 +314,31 @@ prl::FocusMeasures prl::focusMeasures(const cv::Mat& inputImage, int tengKernelS
     return prl::FocusMeasures{m[PRL_FOCUS_LAPM], m[PRL_FOCUS_LAPV], m[PRL_FOCUS_TENG], m[PRL_FOCUS_GLVN]};
 }
 
+// basicDeblur.cpp:33-70.  The reference's order: the empty check, cv::split and convertTo (any depth, any channel count), then
+// cv::GaussianBlur's assertion on the kernel size.
+void prl::basicDeblur(const cv::Mat& inputImage, cv::Mat& outputImage, const size_t gaussianKernelSize, const double sigmaX,
+                      const double sigmaY, const double imageWeight)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image for deblurring is empty");
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsNotImplemented, "prl::basicDeblur: 8-bit images only");   // documented deviation
+    const int cn = inputImage.channels();
+    if (cn > 4) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl::basicDeblur: 8-bit images of 1..4 channels only");
+    if (gaussianKernelSize > (size_t)2147483647) PRL_FAIL_CV(cv::Error::StsBadArg, "prl::basicDeblur: the kernel size does not fit an int");
+    const long long k = (long long)gaussianKernelSize;
+    const double sy = sigmaY <= 0 ? sigmaX : sigmaY;
+    if (k > 0 ? k % 2 != 1 : !(sigmaX > 0 && sy > 0))   // [upstream] createGaussianKernels
+        PRL_FAIL_CV(cv::Error::StsAssert, "ksize.width > 0 && ksize.width % 2 == 1 && ksize.height > 0 && ksize.height % 2 == 1");
+    int kw = 0, kh = 0;
+    int st = prl_hip_gaussian_blur_size(k, k, sigmaX, sigmaY, &kw, &kh);
+    if (st == PRL_ERR_BAD_WINDOW) PRL_FAIL_CV(cv::Error::StsBadArg, "prl::basicDeblur: kernel sides up to 255 only");   // documented deviation
+    if (st != PRL_OK) raise(st);
+    cv::Mat result(inputImage.rows, inputImage.cols, inputImage.type());
+    st = prl_hip_basic_deblur_host(cn, k, sigmaX, sigmaY, imageWeight, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows,
+                                   result.data, result.step);
+    if (st != PRL_OK) raise(st);
+    outputImage = result;
+}
+
 namespace {
 
 constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255
