@@ -561,6 +561,78 @@ int prl_hip_clean_background_lut(uint8_t lut[256]);
 int prl_hip_simple_white_balance_luts(double k, const uint32_t hist[3 * 256], uint8_t luts[3 * 256]);
 int prl_hip_gray_world_luts(double p_norm, int with_max, const uint32_t hist[3 * 256], uint8_t luts[3 * 256]);
 
+/* ---- contrast: cv::CLAHE, cv::equalizeHist, EnhanceLocalContrastByCLAHE (src/imageLibCommon.cpp:327-395) ------------------------ */
+
+#define PRL_CLAHE_MAX_TILES 64   /* tiles a side at most */
+
+/*
+ * cv::CLAHE::apply and cv::equalizeHist on 8-bit pages in device memory, every channel on its own (clahe.hip; the arithmetic as
+ * plain code: prlib_amd/csrc/clahe.h).  Both are [upstream] OpenCV 3.4 / 4.x (clahe.cpp, histogram.cpp), stated from memory.
+ * Every float operation is float32 with one rounding, evaluated left to right as written, never fused; sat_u8 rounds half to even
+ * and clamps.
+ *
+ * CLAHE of one W x H channel, grid tiles_x x tiles_y (cv::createCLAHE's default is 8 x 8), clip_limit a double:
+ *   1. W % tiles_x == 0 and H % tiles_y == 0: the tiles are cut from the page.  Otherwise from copyMakeBorder(src, 0, tiles_y -
+ *      H % tiles_y, 0, tiles_x - W % tiles_x, BORDER_REFLECT_101): BOTH sides grow, a side that divides by a whole `tiles` (16 x
+ *      13 on 8 x 8 becomes 24 x 16).  The border index is borderInterpolate's: a side of 1 gives 0, else the index reflects until
+ *      it lies inside (the pad can exceed the side).  tile_w = ext_w / tiles_x, tile_h = ext_h / tiles_y, area = tile_w * tile_h.
+ *   2. lut_scale = (float)255 / (float)area.  clip = 0 for clip_limit <= 0, else max((int)(clip_limit * area / 256), 1) with the
+ *      product and the quotient in double; a value outside int converts as x86 does, to INT_MIN, hence clip = 1.
+ *   3. Per tile the 256 int bins of the extended page's tile; with clip > 0: clipped = sum of max(h[i] - clip, 0), h[i] = min(h[i],
+ *      clip), every bin += clipped / 256, and with residual = clipped % 256 != 0 and step = max(256 / residual, 1) the loop
+ *      for (i = 0; i < 256 && residual > 0; i += step, --residual) ++h[i] (bin i gets one more where i % step == 0 and i / step <
+ *      residual).  Then sum += h[i], lut[i] = sat_u8((float)sum * lut_scale).
+ *   4. Over the W x H pixels of the page itself: txf = (float)x * (1.0f / tile_w) - 0.5f, tx1 = floor(txf), xa = txf - (float)tx1,
+ *      xa1 = 1.0f - xa, then tx2 = min(tx1 + 1, tiles_x - 1) and tx1 = max(tx1, 0); the same per row with 1.0f / tile_h; with v =
+ *      src(y, x): dst = sat_u8((L(ty1,tx1)[v] * xa1 + L(ty1,tx2)[v] * xa) * ya1 + (L(ty2,tx1)[v] * xa1 + L(ty2,tx2)[v] * xa) * ya).
+ *
+ * equalizeHist of one channel: i = the first non-empty bin, total = W * H.  hist[i] == total: the page comes back as it is (the
+ * reference fills it with i; the table of prl_hip_equalize_hist_lut is then the identity).  Else scale = 255.0f / (float)(total -
+ * hist[i]), lut[v] = 0 for v <= i and, with sum += hist[v] from v = i + 1 on, lut[v] = sat_u8((float)sum * scale); dst = lut[src].
+ *
+ * EnhanceLocalContrastByCLAHE(in, out, clipLimit, equalizeHistFlag): CLAHE on the 8 x 8 grid with clipLimit on every channel,
+ * then, with the flag, equalizeHist of that channel's result.
+ *
+ * Every entry with pages checks in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0);
+ * PRL_ERR_BAD_CHANNELS (channels outside 1..4); PRL_ERR_BAD_ARG (null pointer, negative n_pages, step < row bytes, width or height
+ * above 32768, tiles_x or tiles_y outside 1..PRL_CLAHE_MAX_TILES, a NaN clip_limit, overlapping source and destination).  d_src ==
+ * d_dst with the same strides (in place) is allowed; any other overlap is PRL_ERR_BAD_ARG.  The *_batch_device entries enqueue on
+ * `stream` and do not synchronise; they use the device's cached scratch (per page and channel 1280 bytes per tile, and 1280 for
+ * the equalization).  The *_host entries take one page in host memory.  16-bit pages and larger grids are not provided.
+ */
+
+/* Step 1 and 2 for one page size, on the host: no device is needed.  PRL_ERR_EMPTY, then PRL_ERR_BAD_ARG as above. */
+int prl_hip_clahe_geometry(int width, int height, int tiles_x, int tiles_y, double clip_limit, int* tile_w, int* tile_h, int* ext_w,
+                           int* ext_h, int* clip);
+/* Step 3 for one tile, on the host, by the code the kernel runs.  PRL_ERR_EMPTY for tile_area <= 0; PRL_ERR_BAD_ARG for a null
+ * pointer, clip < 0, or bins that do not sum to tile_area. */
+int prl_hip_clahe_tile_lut(const uint32_t hist[256], int clip, int tile_area, uint8_t lut[256]);
+/* equalizeHist's table from one channel's histogram, on the host, by the code the kernel runs.  PRL_ERR_BAD_ARG for a null
+ * pointer or a sum above 32768 * 32768; PRL_ERR_EMPTY for a sum of 0. */
+int prl_hip_equalize_hist_lut(const uint32_t hist[256], uint8_t lut[256]);
+
+/* Steps 1 to 3: d_luts[page][channel][tile_y][tile_x][256] bytes, the tables step 4 blends (any alignment). */
+int prl_hip_clahe_luts_batch_device(int n_pages, int channels, double clip_limit, int tiles_x, int tiles_y, const uint8_t* d_src,
+                                    size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_luts, void* stream);
+
+int prl_hip_clahe_batch_device(int n_pages, int channels, double clip_limit, int tiles_x, int tiles_y, const uint8_t* d_src,
+                               size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                               size_t dst_step, void* stream);
+int prl_hip_clahe_host(int channels, double clip_limit, int tiles_x, int tiles_y, const uint8_t* src, size_t src_step, int width,
+                       int height, uint8_t* dst, size_t dst_step);
+
+int prl_hip_equalize_hist_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                       int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_equalize_hist_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+
+/* The reference's helper: the 8 x 8 grid; `equalize` != 0: equalizeHist after CLAHE (the interpolation pass counts its own output,
+ * so the pair costs three passes over the pixels). */
+int prl_hip_enhance_local_contrast_batch_device(int n_pages, int channels, double clip_limit, int equalize, const uint8_t* d_src,
+                                                size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                                size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_enhance_local_contrast_host(int channels, double clip_limit, int equalize, const uint8_t* src, size_t src_step, int width,
+                                        int height, uint8_t* dst, size_t dst_step);
+
 /* ---- prl::binarizeMokji and the grey-level co-occurrence matrix ------------------------------------------------------------ */
 
 /*

@@ -81,6 +81,9 @@ EXPORTED_SYMBOLS = [
     "prl_hip_focus_sums_batch_device", "prl_hip_focus_measures_host", "prl_hip_focus_from_sums",
     "prl_hip_basic_deblur_batch_device", "prl_hip_basic_deblur_host", "prl_hip_gaussian_blur_f32_batch_device",
     "prl_hip_gaussian_blur_f32_host", "prl_hip_gaussian_blur_size", "prl_hip_gaussian_kernel_f32",
+    "prl_hip_clahe_geometry", "prl_hip_clahe_tile_lut", "prl_hip_equalize_hist_lut", "prl_hip_clahe_luts_batch_device",
+    "prl_hip_clahe_batch_device", "prl_hip_clahe_host", "prl_hip_equalize_hist_batch_device", "prl_hip_equalize_hist_host",
+    "prl_hip_enhance_local_contrast_batch_device", "prl_hip_enhance_local_contrast_host",
 ]
 
 
@@ -286,6 +289,16 @@ def lib() -> C.CDLL:
         L.prl_hip_gaussian_blur_f32_host.argtypes = [i, ll, ll, d, d, vp, sz, i, i, vp, sz]
         L.prl_hip_gaussian_blur_size.argtypes = [ll, ll, d, d, P(C.c_int), P(C.c_int)]
         L.prl_hip_gaussian_kernel_f32.argtypes = [i, d, vp]
+        L.prl_hip_clahe_geometry.argtypes = [i, i, i, i, d] + [P(C.c_int)] * 5
+        L.prl_hip_clahe_tile_lut.argtypes = [vp, i, i, vp]
+        L.prl_hip_equalize_hist_lut.argtypes = [vp, vp]
+        L.prl_hip_clahe_luts_batch_device.argtypes = [i, i, d, i, i, vp, sz, sz, i, i, vp, vp]
+        L.prl_hip_clahe_batch_device.argtypes = [i, i, d, i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_clahe_host.argtypes = [i, d, i, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_equalize_hist_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_equalize_hist_host.argtypes = [i, vp, sz, i, i, vp, sz]
+        L.prl_hip_enhance_local_contrast_batch_device.argtypes = [i, i, d, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_enhance_local_contrast_host.argtypes = [i, d, i, vp, sz, i, i, vp, sz]
         _lib = L
     return _lib
 

@@ -1,0 +1,24 @@
+// imageLibCommon.h - the part of PRLib's src/imageLibCommon.h that exists here: EnhanceLocalContrastByCLAHE (:151,
+// imageLibCommon.cpp:327-395), declared in the global namespace with the reference's signature, and the two OpenCV functions it is
+// made of as extensions in namespace prl.  Implemented in prl_host.cpp over the C ABI (clahe.hip; the arithmetic is stated in
+// prl_hip.h, "contrast").  The header's other helpers are not provided.
+#pragma once
+
+#include "prl.h"
+
+// cv::createCLAHE() with setClipLimit(CLAHEClipLimit) - the default 8 x 8 grid - applied to every channel of an 8-bit image of 1 to
+// 4 channels, then, with equalizeHistFlag, cv::equalizeHist of that channel's result.  A limit <= 0 means no clipping, as in
+// cv::CLAHE (the reference's callers guard it themselves).  std::invalid_argument("Image for histograms enhancing is empty") for an
+// empty image; cv::Exception StsUnsupportedFormat for a depth other than CV_8U or more than 4 channels, StsBadArg for a NaN limit or a
+// side above 32768 (documented deviations: cv::CLAHE also takes 16-bit images).  outputImage may be inputImage: the result is a new
+// continuous Mat of the input's type, and the input's pixels are never written.
+CV_EXPORTS void EnhanceLocalContrastByCLAHE(cv::Mat& inputImage, cv::Mat& outputImage, double CLAHEClipLimit, bool equalizeHistFlag);
+
+namespace prl {
+
+// Extensions, not in the reference's header: cv::createCLAHE(clipLimit, cv::Size(tilesX, tilesY))->apply and cv::equalizeHist on
+// every channel of an 8-bit image of 1 to 4 channels.  Exceptions as above; StsBadArg also for a grid side outside 1..64.
+CV_EXPORTS void clahe(const cv::Mat& inputImage, cv::Mat& outputImage, double clipLimit = 40.0, int tilesX = 8, int tilesY = 8);
+CV_EXPORTS void equalizeHist(const cv::Mat& inputImage, cv::Mat& outputImage);
+
+}  // namespace prl

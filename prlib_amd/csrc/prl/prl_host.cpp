@@ -4,6 +4,7 @@
 // Only names both have are used; tests/test_cpp_host.py compiles this file against OpenCV's declared signatures
 // (tests/cpp/opencv_api/).  With OpenCV present the colour conversion is OpenCV's own cv::cvtColor, as in the reference.
 #include "prl.h"
+#include "imageLibCommon.h"
 
 #include <cmath>
 #include <cstring>
@@ -337,6 +338,46 @@ void prl::basicDeblur(const cv::Mat& inputImage, cv::Mat& outputImage, const siz
                                    result.data, result.step);
     if (st != PRL_OK) raise(st);
     outputImage = result;
+}
+
+namespace {
+
+// what the three contrast functions share: the reference's empty check, the depth and channel limits, a new Mat for the result
+template <typename Call>
+void contrast_call(const cv::Mat& in, cv::Mat& out, const char* what, Call&& call)
+{
+    if (in.empty()) throw std::invalid_argument("Image for histograms enhancing is empty");
+    if (in.depth() != CV_8U || in.channels() > 4)
+        fail_cv(cv::Error::StsUnsupportedFormat, std::string(what) + ": 8-bit images of 1..4 channels only", what, __LINE__);   // documented deviation
+    cv::Mat result(in.rows, in.cols, in.type());
+    const int st = call(in.channels(), in.data, in.step, in.cols, in.rows, result.data, result.step);
+    if (st != PRL_OK) raise_at(st, what, __LINE__);   // (the exception names the public function, not this helper)
+    out = result;
+}
+
+}  // namespace
+
+// imageLibCommon.cpp:327-395: _1 for one channel, _MCh (split, per channel, merge) for more - the same thing per channel
+void EnhanceLocalContrastByCLAHE(cv::Mat& inputImage, cv::Mat& outputImage, double CLAHEClipLimit, bool equalizeHistFlag)
+{
+    contrast_call(inputImage, outputImage, "EnhanceLocalContrastByCLAHE",
+                  [&](int cn, const unsigned char* s, size_t ss, int w, int h, unsigned char* d, size_t ds) {
+                      return prl_hip_enhance_local_contrast_host(cn, CLAHEClipLimit, equalizeHistFlag ? 1 : 0, s, ss, w, h, d, ds);
+                  });
+}
+
+void prl::clahe(const cv::Mat& inputImage, cv::Mat& outputImage, double clipLimit, int tilesX, int tilesY)
+{
+    contrast_call(inputImage, outputImage, "prl::clahe", [&](int cn, const unsigned char* s, size_t ss, int w, int h, unsigned char* d, size_t ds) {
+        return prl_hip_clahe_host(cn, clipLimit, tilesX, tilesY, s, ss, w, h, d, ds);
+    });
+}
+
+void prl::equalizeHist(const cv::Mat& inputImage, cv::Mat& outputImage)
+{
+    contrast_call(inputImage, outputImage, "prl::equalizeHist", [&](int cn, const unsigned char* s, size_t ss, int w, int h, unsigned char* d, size_t ds) {
+        return prl_hip_equalize_hist_host(cn, s, ss, w, h, d, ds);
+    });
 }
 
 namespace {

@@ -326,6 +326,9 @@ int tone_checks(const PageArgs& a, bool channels_ok, int channels, int oc, bool 
     return batch ? pages_overlap_ok(a, channels, oc, true) : PRL_OK;
 }
 
+}  // namespace
+
+// the histogram pass and the table pass, also for clahe.hip (cv::equalizeHist); they enqueue only
 int hist_launch(int channels, const PageSet& src, int n, int W, int H, unsigned* hist, hipStream_t stream)
 {
     PRL_HIP_CHECK(hipMemsetAsync(hist, 0, (size_t)n * channels * 256 * sizeof(unsigned), stream));
@@ -354,6 +357,8 @@ int lut_launch(int channels, int oc, const PageSet& src, const PageSetOut& dst, 
     PRL_HIP_CHECK(hipGetLastError());
     return PRL_OK;
 }
+
+namespace {
 
 // one table for every page and channel: gamma, the clean-background curve
 int shared_table_run(const PageArgs& a, int channels, int oc, const ToneTab& tab, bool bgnorm_first, void* stream)
