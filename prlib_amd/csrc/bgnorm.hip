@@ -29,6 +29,7 @@ constexpr int SX = 10, SY = 15, THRESH = 60, MINCOUNT = 40, BGVAL = 200, WC = 2,
 constexpr int TILES_PER_BLOCK = 25;                 // 250 page columns + 6 halo columns = 256 threads
 constexpr int COLS_PER_BLOCK = TILES_PER_BLOCK * SX;
 constexpr int FLAG_ROWS = SY + 6;
+constexpr int kLdsMap = 60000;                      // k_bg_maps' LDS copy of a map; an A4 map is 248 x 234 = 58 032 bytes
 
 struct BgGeom {
     int width, height, mw, mh, nx, ny;
@@ -128,8 +129,9 @@ __global__ void __launch_bounds__(256) k_bg_tiles(PageSet src, BgGeom g, uint8_t
 }
 
 // One workgroup per (channel, page).  `maps` rows beyond ny / columns beyond nx are zero (hipMemsetAsync before k_bg_tiles).
+// lds_map_bytes: the largest map that is copied into LDS (kLdsMap unless the test-hooks build's PRL_HIP_BGNORM_LDS_MAP lowers it).
 __global__ void __launch_bounds__(256) k_bg_maps(BgGeom g, int och, uint8_t* __restrict__ maps, unsigned short* __restrict__ inv,
-                                                 int* __restrict__ page_fail)
+                                                 int* __restrict__ page_fail, int lds_map_bytes)
 {
     constexpr int MAX_MW = 4096;
     __shared__ uint8_t na[MAX_MW];
@@ -138,10 +140,9 @@ __global__ void __launch_bounds__(256) k_bg_maps(BgGeom g, int och, uint8_t* __r
     const int w = g.mw, h = g.mh, nx = g.nx, ny = g.ny;
     // the map itself is tiny (248 x 234 bytes for A4): work on an LDS copy when it fits (the column fills are chains of
     // dependent accesses: 0.61 ms for 64 gray pages' maps from memory, 0.27 ms from LDS), on the global one otherwise
-    constexpr int LDS_MAP = 60000;  // an A4 map is 248 x 234 = 58 032 bytes
-    __shared__ uint8_t lmap[LDS_MAP];
+    __shared__ uint8_t lmap[kLdsMap];
     uint8_t* gm = maps + (size_t)page * g.map_page + (size_t)c * w * h;
-    const bool in_lds = w * h <= LDS_MAP;
+    const bool in_lds = w * h <= lds_map_bytes;  // (the host keeps lds_map_bytes <= kLdsMap)
     if (in_lds)
         for (int i = t; i < w * h; i += 256) lmap[i] = gm[i];
     uint8_t* m = in_lds ? lmap : gm;  // (phases are separated by workgroup barriers; no volatile: the memory path stays cached)
@@ -283,7 +284,7 @@ __global__ void __launch_bounds__(256) k_bg_apply(PageSet src, PageSetOut dst, B
 }  // namespace
 
 int bgnorm_run(int n_pages, int channels, const PageSet& src, int width, int height, const PageSetOut& dst, void* work,
-               hipStream_t stream);
+               hipStream_t stream, uint8_t* out_raw, unsigned short* out_inv, int* out_fail);
 size_t bgnorm_work_bytes(int n_pages, int channels, int width, int height);
 
 static BgGeom make_geom(int channels, int width, int height)
@@ -305,8 +306,11 @@ size_t bgnorm_work_bytes(int n_pages, int channels, int width, int height)
 }
 
 // work: [u8 maps][u16 inverse maps][int fail flag per page]
+// out_raw / out_inv / out_fail (device memory; all null from the product entries, all set from the test-hooks entry): dense copies,
+// on the same stream, of the tile maps as k_bg_tiles left them (n x och x mh x mw bytes, taken before k_bg_maps fills them in), of
+// the inverse maps (n x och x mh x mw u16) and of the fail flags (n ints).
 int bgnorm_run(int n_pages, int channels, const PageSet& src, int width, int height, const PageSetOut& dst, void* work,
-               hipStream_t stream)
+               hipStream_t stream, uint8_t* out_raw, unsigned short* out_inv, int* out_fail)
 {
     const BgGeom g = make_geom(channels, width, height);
     const int och = channels == 1 ? 1 : 3;
@@ -322,8 +326,13 @@ int bgnorm_run(int n_pages, int channels, const PageSet& src, int width, int hei
         else hipLaunchKernelGGL(k_bg_tiles<4>, grid, dim3(256), 0, stream, src, g, maps);
         PRL_HIP_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(k_bg_maps, dim3((unsigned)och, (unsigned)n_pages), dim3(256), 0, stream, g, och, maps, inv, fail);
+    const size_t dense = (size_t)och * g.mw * g.mh;
+    if (out_raw) PRL_HIP_CHECK(hipMemcpy2DAsync(out_raw, dense, maps, g.map_page, dense, (size_t)n_pages, hipMemcpyDeviceToDevice, stream));
+    const int lds_map_bytes = std::min(kLdsMap, env_knobs().bgnorm_lds_map);
+    hipLaunchKernelGGL(k_bg_maps, dim3((unsigned)och, (unsigned)n_pages), dim3(256), 0, stream, g, och, maps, inv, fail, lds_map_bytes);
     PRL_HIP_CHECK(hipGetLastError());
+    if (out_inv) PRL_HIP_CHECK(hipMemcpy2DAsync(out_inv, dense * 2, inv, g.inv_page * 2, dense * 2, (size_t)n_pages, hipMemcpyDeviceToDevice, stream));
+    if (out_fail) PRL_HIP_CHECK(hipMemcpyAsync(out_fail, fail, (size_t)n_pages * sizeof(int), hipMemcpyDeviceToDevice, stream));
     const int apx = channels == 1 ? ApplyGeo<1>::APX : ApplyGeo<3>::APX;
     const dim3 agrid((unsigned)(((size_t)((width + apx - 1) / apx) * height + 255) / 256), (unsigned)n_pages);
     if (channels == 1) hipLaunchKernelGGL(k_bg_apply<1>, agrid, dim3(256), 0, stream, src, dst, g, inv, fail);
@@ -337,6 +346,30 @@ int bgnorm_run(int n_pages, int channels, const PageSet& src, int width, int hei
 
 using namespace prl_hip;
 
+static int bgnorm_chunk(int n_pages) { return stage_chunk(n_pages, 0, 0, 16384); }   // pages per launch sequence
+
+// The device entry and the test-hooks entry below (out_*: see bgnorm_run; set only with the pages of one chunk at most).
+static int bgnorm_batch(const PageArgs& a, int channels, uint8_t* out_raw, unsigned short* out_inv, int* out_fail, void* stream)
+{
+    const int n_pages = a.n_pages, width = a.width, height = a.height;
+    int st = pages_nonempty(a);  // backgroundNormalization.cpp:40-43
+    if (st != PRL_OK) return st;
+    if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;  // formatConvert.cpp:103-104
+    if ((st = pages_rows_ok(a, channels, channels == 1 ? 1 : 3, true)) != PRL_OK) return st;
+    if (height > 65535 || width > 40950) return PRL_ERR_BAD_ARG;  // grid.y; k_bg_maps' column flags
+    if (n_pages == 0) return PRL_OK;
+    const int chunk = bgnorm_chunk(n_pages);
+    WorkScope w;
+    st = w.open(stream, bgnorm_work_bytes(chunk, channels, width, height), 0, 0);
+    if (st != PRL_OK) return st;
+    for (int first = 0; first < n_pages; first += chunk) {
+        st = bgnorm_run(std::min(chunk, n_pages - first), channels, src_pages(a, first), width, height, dst_pages(a, first), w.scratch(),
+                        w.stream, out_raw, out_inv, out_fail);
+        if (st != PRL_OK) return st;
+    }
+    return PRL_OK;
+}
+
 extern "C" {
 
 int prl_hip_bgnorm_out_channels(int channels) { return channels == 1 ? 1 : 3; }
@@ -344,24 +377,24 @@ int prl_hip_bgnorm_out_channels(int channels) { return channels == 1 ? 1 : 3; }
 int prl_hip_bgnorm_batch_device(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
                                 int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream)
 {
-    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
-    int st = pages_nonempty(a);  // backgroundNormalization.cpp:40-43
-    if (st != PRL_OK) return st;
-    if (channels != 1 && channels != 3 && channels != 4) return PRL_ERR_BAD_CHANNELS;  // formatConvert.cpp:103-104
-    if ((st = pages_rows_ok(a, channels, channels == 1 ? 1 : 3, true)) != PRL_OK) return st;
-    if (height > 65535 || width > 40950) return PRL_ERR_BAD_ARG;  // grid.y; k_bg_maps' column flags
-    if (n_pages == 0) return PRL_OK;
-    const int chunk = stage_chunk(n_pages, 0, 0, 16384);
-    WorkScope w;
-    st = w.open(stream, bgnorm_work_bytes(chunk, channels, width, height), 0, 0);
-    if (st != PRL_OK) return st;
-    for (int first = 0; first < n_pages; first += chunk) {
-        st = bgnorm_run(std::min(chunk, n_pages - first), channels, src_pages(a, first), width, height, dst_pages(a, first), w.scratch(),
-                        w.stream);
-        if (st != PRL_OK) return st;
-    }
-    return PRL_OK;
+    return bgnorm_batch(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
+                        nullptr, nullptr, nullptr, stream);
 }
+
+#ifdef PRL_TEST_HOOKS
+// libprlib_hip_testhooks.so only: the product entry's own launch sequence, and what its stages left in scratch.  d_raw: n_pages x
+// och x mh x mw bytes, the tile maps of k_bg_tiles before k_bg_maps fills their holes; d_inv: as many u16, the inverse maps; d_fail:
+// n_pages ints; all three in device memory (och = 1 or 3, mw = ceil(width / 10), mh = ceil(height / 15)).  The pages of one chunk at
+// most (16384, or what PRL_HIP_STAGE_CHUNK leaves of it: the scratch of a later chunk overwrites the one before it).
+int prl_hip_internal_bgnorm_maps(int n_pages, int channels, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                 int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, uint8_t* d_raw,
+                                 unsigned short* d_inv, int* d_fail, void* stream)
+{
+    if (n_pages > bgnorm_chunk(n_pages) || !d_raw || !d_inv || !d_fail) return PRL_ERR_BAD_ARG;
+    return bgnorm_batch(PageArgs{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step}, channels,
+                        d_raw, d_inv, d_fail, stream);
+}
+#endif
 
 int prl_hip_bgnorm_host(int channels, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
 {

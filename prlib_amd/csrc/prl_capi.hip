@@ -112,6 +112,7 @@ const EnvKnobs& env_knobs()
         k.gmorph_literal = geti("PRL_HIP_GMORPH_LITERAL", 0) != 0;
         k.lines_bytes = geti("PRL_HIP_LINES_BYTES", 0) != 0;
         k.stage_chunk_pages = (int)std::max(0ll, std::min(65535ll, geti("PRL_HIP_STAGE_CHUNK", 0)));
+        k.bgnorm_lds_map = (int)std::max(0ll, std::min(60000ll, geti("PRL_HIP_BGNORM_LDS_MAP", 60000)));
         k.segmax_cap = (unsigned)std::max(64ll, std::min(1ll << 20, geti("PRL_HIP_SEGMAX_CAP", 1 << 20)));
         k.force_exact = geti("PRL_HIP_FORCE_EXACT", 0) != 0;
 #endif

@@ -133,6 +133,7 @@ struct EnvKnobs {
     bool gmorph_literal = false;  // PRL_HIP_GMORPH_LITERAL=1  the by-the-definition kernel for every element (gmorph.hip)
     bool lines_bytes = false;     // PRL_HIP_LINES_BYTES=1     removeLines' openings on byte masks through k_gm_span (lines.hip)
     int stage_chunk_pages = 0;    // PRL_HIP_STAGE_CHUNK=n     (tests) the stage entries take at most n pages per chunk (stage_chunk below; 0: off)
+    int bgnorm_lds_map = 60000;   // PRL_HIP_BGNORM_LDS_MAP=n  (tests) the largest map in bytes k_bg_maps copies into LDS (bgnorm.hip; 0: every map stays in global memory)
 };
 const EnvKnobs& env_knobs();
 

@@ -26,7 +26,7 @@ namespace prl_hip {
 
 // bgnorm.hip
 int bgnorm_run(int n_pages, int channels, const PageSet& src, int width, int height, const PageSetOut& dst, void* work,
-               hipStream_t stream);
+               hipStream_t stream, uint8_t* out_raw, unsigned short* out_inv, int* out_fail);
 size_t bgnorm_work_bytes(int n_pages, int channels, int width, int height);
 
 namespace {
@@ -376,7 +376,7 @@ int shared_table_run(const PageArgs& a, int channels, int oc, const ToneTab& tab
         const int n = std::min(chunk, a.n_pages - first);
         const PageSetOut d = dst_pages(a, first);
         if (bgnorm_first) {
-            st = bgnorm_run(n, channels, src_pages(a, first), a.width, a.height, d, w.scratch(), hs);
+            st = bgnorm_run(n, channels, src_pages(a, first), a.width, a.height, d, w.scratch(), hs, nullptr, nullptr, nullptr);
             if (st != PRL_OK) return st;
             st = lut_launch(oc, oc, as_source(d), d, n, a.width, a.height, lut, 0, hs);
         } else {
