@@ -821,6 +821,143 @@ int prl_hip_gaussian_blur_f32_host(int channels, long long kernel_w, long long k
 int prl_hip_gaussian_blur_size(long long kernel_w, long long kernel_h, double sigma_x, double sigma_y, int* out_w, int* out_h);
 int prl_hip_gaussian_kernel_f32(int n, double sigma, float* w);
 
+/* ---- the 8-bit cv::GaussianBlur: 8.8 fixed-point weights, integer arithmetic (blur8.hip, gauss8.h) ------------ */
+
+/*
+ * cv::GaussianBlur(src, dst, Size(kernel_w, kernel_h), sigma_x, sigma_y) on 8-bit pages of 1 to 4 interleaved channels, as the
+ * OpenCV line 4.1.1 and later filters a CV_8U image without an accelerator [upstream: smooth.dispatch.cpp / fixedpoint.inl.hpp,
+ * stated from memory; parity unpinned, DESIGN.md §2].  All of it is integer: exact and independent of the order of summation.
+ *   sides             each odd and in 1 .. PRL_GAUSS_MAX_SIDE (a side <= 0, which OpenCV derives from sigma, is not taken).
+ *   sigmas            sigma_y <= 0 -> sigma_y = sigma_x; a sigma <= 0 for a side of n is ((n - 1) * 0.5 - 1) * 0.3 + 0.8.
+ *   float64 weights   sigma <= 0 and n in {1, 3, 5, 7}: the tables {1}, {.25, .5, .25}, {.0625, .25, .375, .25, .0625},
+ *                     {.03125, .109375, .21875, .28125, .21875, .109375, .03125}; otherwise k_i = exp(-0.5 / sigma^2 * (i - (n - 1) / 2)^2)
+ *                     divided by the sum of all k (index order).
+ *   8.8 weights       by error diffusion: err = 0; for i = 0 .. n / 2 - 1: adj = k_i * 256 + err, v = cvRound(adj) (ties to even),
+ *                     err = adj - v, w_i = w_(n-1-i) = v; the centre w_(n/2) = 256 - the sum of the others.  A side sums to 256.
+ *                     Side 3 at sigma 0: 64 128 64; 5: 16 64 96 64 16; 9: 4 13 30 51 60 51 30 13 4.  The centre need not be the
+ *                     largest weight (25 at sigma 0: 24 between two 25s).  OpenCV evaluates exp in soft-float, this library with
+ *                     std::exp: no adj of any odd n <= 255 (sigma 0, or sigma 0.1, 0.2 .. 100) lies within 1e-8 of a rounding tie,
+ *                     far above the error of either (tests/test_localotsu_cpu.py re-derives the margin).
+ *   the filter        per channel, with R(p, len) = cv::borderInterpolate(p, len, BORDER_REFLECT_101) (as for pyrDown above), rx = nx / 2,
+ *                     ry = ny / 2:  h(x, y) = sum_i wx_i * p(R(x + i - rx, W), y)  (at most 255 * 256: 16 bits),
+ *                     dst(x, y) = (sum_j wy_j * h(x, R(y + j - ry, H)) + 32768) >> 16  (32 bits).  Nothing saturates, since a side
+ *                     sums to 256; a 1 x 1 kernel copies; thin pages are filtered through their reflections.
+ * NOT restated: the rule of OpenCV 3.4.x - 4.1.0 (every weight rounded on its own) and accelerator builds (IPP, OpenVX).  Another
+ * weight rule is a change of the host table alone: the kernel takes the weights as they come (prl_hip_sep_filter_u8_batch_device).
+ * One fused kernel (blur8.hip): row pass into an LDS ring of 16-bit row results, column pass, the rounded byte; its only global
+ * write is the destination.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_WINDOW (a side <= 0, even
+ * or above PRL_GAUSS_MAX_SIDE); PRL_ERR_BAD_ARG (channels outside 1..4; a NaN or infinite sigma; the explicit-weight entry: a null
+ * weight pointer or a side whose weights sum to more than 256; a null page pointer; negative n_pages; a step below the row bytes;
+ * width or height above 32768; source and destination sharing a byte).  n_pages == 0 is PRL_OK.
+ */
+
+/* The n 8.8 weights of a side, on the host, no device needed.  PRL_ERR_BAD_WINDOW for n <= 0, even or above PRL_GAUSS_MAX_SIDE;
+ * PRL_ERR_BAD_ARG for a null pointer or a NaN or infinite sigma. */
+int prl_hip_gaussian_kernel_u8(int n, double sigma, uint16_t* w);
+
+/*
+ * The filter alone with explicit 8.8 weights in host memory (wx: nx weights in tap order, wy: ny; they need not be symmetric): the
+ * seam the kernel is tested at.  n pages per call; pages and rows may be strided.  Enqueues on `stream` and does not synchronise;
+ * needs no workspace; d_src is never written.
+ */
+int prl_hip_sep_filter_u8_batch_device(int n_pages, int channels, const uint16_t* wx, int nx, const uint16_t* wy, int ny,
+                                       const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
+                                       uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_gaussian_blur_u8_batch_device(int n_pages, int channels, int kernel_w, int kernel_h, double sigma_x, double sigma_y,
+                                          const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width, int height,
+                                          uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+/* One page in host memory, through the staging area.  Same checks (no page count; the two may not overlap either). */
+int prl_hip_gaussian_blur_u8_host(int channels, int kernel_w, int kernel_h, double sigma_x, double sigma_y, const uint8_t* src,
+                                  size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+
+/* ---- CannyEdgeDetection (src/imageLibCommon.cpp:244-324): the edge stage of binarizeLocalOtsu, COCOCLUST and FBCITB (edgedet.hip) --- */
+
+/*
+ * CannyEdgeDetection(image, result, GaussianBlurKernelSize, CannyUpperThresholdCoeff, CannyLowerThresholdCoeff, CannyMorphIters)
+ * on 8-bit pages of 1 to 4 interleaved channels -> width x height maps of 0 / 255.  Per channel:
+ *   1. the 8-bit cv::GaussianBlur above with Size(blur_size, blur_size) and sigma 0
+ *   2. t = the Otsu value of the blurred plane (getThreshVal_Otsu_8u: float64 scan, scale 1 / (width * height)), an integer in 0 .. 255
+ *   3. upper = upper_coeff * t, lower = lower_coeff * upper, in float64
+ *   4. cv::Canny(lower, upper) as stated under "pyramid, edge map, resize" (aperture 3, L1 magnitude)
+ *   5. morph_iterations > 0: cv::dilate 3 x 3 that many times, then cv::erode as many; < 0: erode, then dilate
+ * and the channels' maps are OR-ed.  The thresholds differ per page and per channel; t stays on the device: the host uploads the
+ * (low, high) pair of each of the 256 values t can take, and the kernel of step 4 looks its page's pair up.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY; PRL_ERR_BAD_ARG in the reference's order (blur_size < 3; a
+ * coefficient outside [0, 1], a NaN included; lower_coeff > upper_coeff; an even blur_size - cv::GaussianBlur's assertion);
+ * PRL_ERR_BAD_WINDOW (blur_size above PRL_GAUSS_MAX_SIDE); PRL_ERR_BAD_CHANNELS (not 1 .. 4); PRL_ERR_BAD_ARG (|morph_iterations| above
+ * 255; a null pointer; negative n_pages; a step below the row bytes; width or height above 32768; source and destination sharing
+ * a byte).  n_pages == 0 is PRL_OK.  Waits for the stream (cv::Canny's hysteresis does).
+ */
+int prl_hip_canny_edge_detection_batch_device(int n_pages, int channels, int blur_size, double upper_coeff, double lower_coeff,
+                                              int morph_iterations, const uint8_t* d_src, size_t src_page_stride, size_t src_step,
+                                              int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, void* stream);
+int prl_hip_canny_edge_detection_host(int channels, int blur_size, double upper_coeff, double lower_coeff, int morph_iterations,
+                                      const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step);
+
+/* ---- binarizeLocalOtsu (src/binarizations/binarizeLocalOtsu.cpp:37-163): localotsu.hip, contour.h ------------------------------- */
+
+/*
+ * The cv::boundingRect (x, y, width, height) of every contour of at least 3 points that
+ * cv::findContours(map, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) finds on an 8UC1 map in host memory (non-zero = foreground), in
+ * discovery order: what binarizeLocalOtsu keeps of its contours (RemoveChildrenContours on a flat hierarchy drops the contours of
+ * fewer than 3 points).  The scan is OpenCV's retrieval mode 0, literally [upstream, from memory; parity unpinned]: per row, lnbd
+ * starts at the frame column; at a change prev -> p that is not 0 -> 1: nothing if p != 0 or prev < 1, else a hole start, which
+ * moves lnbd to x - 1 when prev is a traced pixel (prev & -2) and is never traced; an outer start (0 -> 1) is skipped when the pixel
+ * at lnbd is positive; after either, prev = p (read again after a trace) and lnbd = x when prev & -2.  Borders are followed and
+ * marked as cv::findContours does (see "document contour").  The scan is restated as written, not replaced by the topological
+ * rule "the outermost component".  *n_found: all contours; *n_kept: those of at least 3 points.  With n_kept > max_rects only the counts are
+ * written (call again with room).  Host code, no device: plain C++ on the calling thread.
+ * PRL_ERR_EMPTY for width or height <= 0; PRL_ERR_BAD_ARG for a null pointer, a step below the width, a negative max_rects or a
+ * side above 32768.
+ */
+int prl_hip_external_rects(const uint8_t* map, size_t step, int width, int height, int32_t* rects, int max_rects, int* n_found,
+                           int* n_kept);
+
+#define PRL_RECT_OTSU_SMALL_AREA 4096   /* a rectangle of at most this many pixels is one wavefront's; a larger one is split */
+
+/*
+ * The per-rectangle Otsu and the paint: d_dst = 255 everywhere except, for every rectangle, 0 where (v ^ 255) != 0 with
+ * v = p > thr ? imax : 0, p the byte of the gray page, imax = saturate_u8(cvRound(max_value)) and thr = getThreshVal_Otsu_8u of the
+ * rectangle's own histogram with scale = 1 / (w * h), in float64 (cv::threshold(THRESH_OTSU) on a copy of the rectangle, then
+ * setTo(0, v ^ 255): binarizeLocalOtsu.cpp:145-160).  So with imax == 255 a pixel of a rectangle is black iff p <= thr, and with
+ * any other imax the whole rectangle is black.  Rectangles may overlap: only 0 is ever stored, the result does not depend on
+ * their order.  rect_offsets (HOST memory, n_pages + 1 values, the first 0, not decreasing; copied before the call returns): the rectangles of page i are
+ * d_rects[4 * rect_offsets[i]] .. d_rects[4 * rect_offsets[i + 1]] (DEVICE memory: x, y, width, height each); a rectangle that does
+ * not lie on the page is ignored.  d_thresholds (device, one int32 per rectangle) receives every thr; NULL: not wanted.
+ * A rectangle of at most PRL_RECT_OTSU_SMALL_AREA pixels is one wavefront's work (bins in LDS, scan, store); a larger one is split
+ * across workgroups (bins by atomics into a slab of the workspace, a threshold launch, a paint launch).  Enqueues on `stream`.
+ * Checked in this order: PRL_ERR_EMPTY; PRL_ERR_BAD_ARG (max_value outside [0, 255] or a NaN; a null page pointer; negative n_pages;
+ * a step below the width; a side above 32768; gray and destination sharing a byte; null or malformed rect_offsets; d_rects null
+ * with rectangles to read).
+ */
+int prl_hip_rect_otsu_batch_device(int n_pages, const int32_t* rect_offsets, const int32_t* d_rects, double max_value, const uint8_t* d_gray,
+                                   size_t gray_page_stride, size_t gray_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                                   size_t dst_step, int32_t* d_thresholds, void* stream);
+
+/*
+ * prl::binarizeLocalOtsu(in, out, maxValue = 255, CLAHEClipLimit = 0, GaussianBlurKernelSize = 19, CannyUpperThresholdCoeff = 0.15,
+ * CannyLowerThresholdCoeff = 0.01, CannyMorphIters = 1) on pages of 1, 3 or 4 interleaved channels -> width x height masks:
+ *   1. gray: a colour page through cv::COLOR_RGB2GRAY, (4899 c0 + 9617 c1 + 1868 c2 + 8192) >> 14 (the reference converts its BGR
+ *      pages as RGB: the weights of prl_hip_bgr2gray_batch_device, swapped); of four channels the fourth is ignored
+ *   2. clahe_clip_limit > 0: EnhanceLocalContrastByCLAHE(clip, equalize = true) on the gray page
+ *   3. CannyEdgeDetection above; 4. cv::dilate 3 x 3, three iterations
+ *   5. one read-back of the edge maps; 6. prl_hip_external_rects of each on the host thread pool
+ *   7. the rectangles go up; prl_hip_rect_otsu_batch_device's kernels on the gray page of step 2 (not the blurred one)
+ * n_found / n_kept (host memory, n_pages values each, or NULL): the contours and the rectangles of every page.  A page without
+ * contours (n_found == 0) is all 255; the C++ function throws the reference's std::invalid_argument for it.
+ * Checked in this order: PRL_ERR_EMPTY; PRL_ERR_BAD_ARG (max_value outside [0, 255]; CannyEdgeDetection's argument checks in its
+ * order); PRL_ERR_BAD_WINDOW (blur_size above PRL_GAUSS_MAX_SIDE); PRL_ERR_BAD_CHANNELS (not 1, 3 or 4); PRL_ERR_BAD_ARG (a NaN clip
+ * limit, |morph_iterations| above 255, then the pages as above).  Waits for the stream.
+ */
+int prl_hip_binarize_local_otsu_batch_device(int n_pages, int channels, double max_value, double clahe_clip_limit, int blur_size,
+                                             double upper_coeff, double lower_coeff, int morph_iterations, const uint8_t* d_src,
+                                             size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                             size_t dst_page_stride, size_t dst_step, int32_t* n_found, int32_t* n_kept, void* stream);
+int prl_hip_binarize_local_otsu_host(int channels, double max_value, double clahe_clip_limit, int blur_size, double upper_coeff,
+                                     double lower_coeff, int morph_iterations, const uint8_t* src, size_t src_step, int width, int height,
+                                     uint8_t* dst, size_t dst_step, int32_t* n_found, int32_t* n_kept);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

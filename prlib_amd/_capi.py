@@ -84,6 +84,10 @@ EXPORTED_SYMBOLS = [
     "prl_hip_clahe_geometry", "prl_hip_clahe_tile_lut", "prl_hip_equalize_hist_lut", "prl_hip_clahe_luts_batch_device",
     "prl_hip_clahe_batch_device", "prl_hip_clahe_host", "prl_hip_equalize_hist_batch_device", "prl_hip_equalize_hist_host",
     "prl_hip_enhance_local_contrast_batch_device", "prl_hip_enhance_local_contrast_host",
+    "prl_hip_gaussian_kernel_u8", "prl_hip_sep_filter_u8_batch_device", "prl_hip_gaussian_blur_u8_batch_device",
+    "prl_hip_gaussian_blur_u8_host", "prl_hip_canny_edge_detection_batch_device", "prl_hip_canny_edge_detection_host",
+    "prl_hip_external_rects", "prl_hip_rect_otsu_batch_device", "prl_hip_binarize_local_otsu_batch_device",
+    "prl_hip_binarize_local_otsu_host",
 ]
 
 
@@ -299,6 +303,16 @@ def lib() -> C.CDLL:
         L.prl_hip_equalize_hist_host.argtypes = [i, vp, sz, i, i, vp, sz]
         L.prl_hip_enhance_local_contrast_batch_device.argtypes = [i, i, d, i, vp, sz, sz, i, i, vp, sz, sz, vp]
         L.prl_hip_enhance_local_contrast_host.argtypes = [i, d, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_gaussian_kernel_u8.argtypes = [i, d, vp]
+        L.prl_hip_sep_filter_u8_batch_device.argtypes = [i, i, vp, i, vp, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_gaussian_blur_u8_batch_device.argtypes = [i, i, i, i, d, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_gaussian_blur_u8_host.argtypes = [i, i, i, d, d, vp, sz, i, i, vp, sz]
+        L.prl_hip_canny_edge_detection_batch_device.argtypes = [i, i, i, d, d, i, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_canny_edge_detection_host.argtypes = [i, i, d, d, i, vp, sz, i, i, vp, sz]
+        L.prl_hip_external_rects.argtypes = [vp, sz, i, i, vp, i, P(C.c_int), P(C.c_int)]
+        L.prl_hip_rect_otsu_batch_device.argtypes = [i, vp, vp, d, vp, sz, sz, i, i, vp, sz, sz, vp, vp]
+        L.prl_hip_binarize_local_otsu_batch_device.argtypes = [i, i, d, d, i, d, d, i, vp, sz, sz, i, i, vp, sz, sz, vp, vp, vp]
+        L.prl_hip_binarize_local_otsu_host.argtypes = [i, d, d, i, d, d, i, vp, sz, i, i, vp, sz, vp, vp]
         _lib = L
     return _lib
 

@@ -35,6 +35,10 @@ constexpr int kLkWords = 4;    // ... x 64-column words; one lane per word
 
 struct CannyCfg {
     int W, H, low, high;
+    // per-page thresholds (CannyEdgeDetection, edgedet.hip): page i takes the pair lut[2 t], lut[2 t + 1] of its t = page_t[i], both
+    // in device memory; null: low / high above for every page
+    const int* lut = nullptr;
+    const int* page_t = nullptr;
 };
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
@@ -49,6 +53,12 @@ __global__ __launch_bounds__(kCnTW) void k_canny_classes(CannyCfg c, PageSet src
     const int t = threadIdx.x, x0 = blockIdx.x * kCnTW, x = x0 + t, page = blockIdx.z;
     const uint8_t* sp = src.page(page);
     const int y0 = blockIdx.y * kCnRows, y1 = min(y0 + kCnRows, c.H);
+    int low = c.low, high = c.high;
+    if (c.page_t) {   // uniform: scalar loads
+        const int tv = c.page_t[page];
+        low = c.lut[2 * tv];
+        high = c.lut[2 * tv + 1];
+    }
     int dx_prev = 0, dy_prev = 0, dx_cur = 0, dy_cur = 0;   // this lane's column: rows j - 2 and j - 1
     for (int j = y0 - 2; j <= y1 + 1; ++j) {
         {
@@ -100,7 +110,7 @@ __global__ __launch_bounds__(kCnTW) void k_canny_classes(CannyCfg c, PageSet src
                 const unsigned short* mc = mg[(y + 3) % 3] + t + 1;
                 const unsigned short* md = mg[(y + 4) % 3] + t + 1;
                 const int m = mc[0], dx = dx_prev, dy = dy_prev;
-                if (m > c.low) {
+                if (m > low) {
                     const int ax = abs(dx), ay = abs(dy) << 15, tg = ax * 13573;
                     bool is_max;
                     if (ay < tg) is_max = m > (int)mc[-1] && m >= (int)mc[1];
@@ -109,7 +119,7 @@ __global__ __launch_bounds__(kCnTW) void k_canny_classes(CannyCfg c, PageSet src
                         const int s = (dx ^ dy) < 0 ? -1 : 1;
                         is_max = m > (int)mu[-s] && m > (int)md[s];
                     }
-                    if (is_max) cls = m > c.high ? 2 : 0;
+                    if (is_max) cls = m > high ? 2 : 0;
                 }
                 if (!BITS) dst.page(page)[(size_t)y * dst.step + x] = (uint8_t)cls;
             }
@@ -393,12 +403,24 @@ int canny_pages_per_chunk(int n_pages, int W, int H, size_t extra_per_page)
     return stage_chunk(n_pages, work_per_page(g) + extra_per_page, (size_t)4 << 30, std::min(65535, by_tiles));
 }
 
+void canny_threshold_table(double upper_coeff, double lower_coeff, int* lut)
+{
+    for (int t = 0; t < 256; ++t) {   // imageLibCommon.cpp:302-306, in float64
+        const double upper = upper_coeff * (double)t;
+        const double lower = lower_coeff * upper;
+        canny_thresholds(lower, upper, &lut[2 * t], &lut[2 * t + 1]);
+    }
+}
+
 int canny_run(int W, int H, int low, int high, const PageSet& s, const PageSetOut& d, int n, uint8_t* work, unsigned* h_flags, hipStream_t hs,
-              int channels)
+              int channels, const int* d_lut, const int* d_page_t)
 {
     const LinkGeom g = link_geom(W, H);
     const LinkWork w = link_work(g, n, work);
-    const int st = classes_launch(CannyCfg{W, H, low, high}, true, s, d, n, g, w, hs, channels);
+    CannyCfg cfg{W, H, low, high};
+    cfg.lut = d_lut;
+    cfg.page_t = d_page_t;
+    const int st = classes_launch(cfg, true, s, d, n, g, w, hs, channels);
     if (st != PRL_OK) return st;
     return link_and_expand(g, w, n, d, h_flags, nullptr, hs);
 }

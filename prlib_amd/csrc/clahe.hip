@@ -339,48 +339,72 @@ int clahe_interp_launch(int C, const PageSet& s, const PageSetOut& d, int n, int
     return PRL_OK;
 }
 
+// The workspace of a chunk of pages: [tile bins | tile tables | the pages' bins | the pages' tables], each block 256-byte aligned
+struct ContrastWork {
+    size_t p_thist, p_tlut, p_hist, p_lut;   // bytes per page
+    size_t per_page() const { return p_thist + p_tlut + p_hist + p_lut + 4 * 256; }
+    size_t bytes(int chunk) const { return r256(chunk * p_thist) + r256(chunk * p_tlut) + r256(chunk * p_hist) + r256(chunk * p_lut); }
+};
+
+ContrastWork contrast_work(int C, const ContrastSpec& sp, bool luts_out)
+{
+    const size_t tiles = sp.clahe ? (size_t)sp.tiles_x * sp.tiles_y : 0;
+    ContrastWork cw;
+    cw.p_thist = (size_t)C * tiles * 256 * sizeof(unsigned);
+    cw.p_tlut = luts_out ? 0 : (size_t)C * tiles * 256;
+    cw.p_hist = sp.equalize ? (size_t)C * 256 * sizeof(unsigned) : 0;
+    cw.p_lut = sp.equalize ? (size_t)C * 256 : 0;
+    return cw;
+}
+
+// n pages (at most the `chunk` the workspace `work` was sized for) from s into d; luts_out: the tile tables of these pages go
+// there and no pixel is written.  Enqueues only.
+int contrast_chunk(int C, const ContrastSpec& sp, const PageSet& s, const PageSetOut& d, int n, int W, int H, const ContrastWork& cw,
+                   int chunk, uint8_t* work, uint8_t* luts_out, hipStream_t hs)
+{
+    const ClaheGeom g = clahe_geometry(W, H, sp.tiles_x, sp.tiles_y, sp.clip_limit);
+    const size_t tiles = sp.clahe ? (size_t)sp.tiles_x * sp.tiles_y : 0;
+    unsigned* d_thist = reinterpret_cast<unsigned*>(work);
+    uint8_t* d_tlut = work + r256(chunk * cw.p_thist);
+    unsigned* d_hist = reinterpret_cast<unsigned*>(d_tlut + r256(chunk * cw.p_tlut));
+    uint8_t* d_lut = reinterpret_cast<uint8_t*>(d_hist) + r256(chunk * cw.p_hist);
+    int st;
+    if (sp.clahe) {
+        st = clahe_hist_launch(C, s, n, W, H, g, d_thist, hs);
+        if (st != PRL_OK) return st;
+        uint8_t* tl = luts_out ? luts_out : d_tlut;
+        const int n_tiles = (int)((size_t)n * C * tiles);
+        hipLaunchKernelGGL(k_clahe_luts, dim3((unsigned)((n_tiles + 3) / 4)), dim3(kClaheThreads), 0, hs, n_tiles, g.clip, g.lut_scale,
+                           d_thist, tl);
+        PRL_HIP_CHECK(hipGetLastError());
+        if (luts_out) return PRL_OK;
+        st = clahe_interp_launch(C, s, d, n, W, H, g, tl, sp.equalize ? d_hist : nullptr, hs);
+        if (st != PRL_OK) return st;
+    } else {
+        st = hist_launch(C, s, n, W, H, d_hist, hs);
+        if (st != PRL_OK) return st;
+    }
+    if (!sp.equalize) return PRL_OK;
+    hipLaunchKernelGGL(k_equalize_derive, dim3((unsigned)((n * C + 63) / 64)), dim3(64), 0, hs, n * C, d_hist, d_lut);
+    PRL_HIP_CHECK(hipGetLastError());
+    return lut_launch(C, C, sp.clahe ? as_source(d) : s, d, n, W, H, d_lut, (size_t)C * 256, hs);   // (in place after CLAHE)
+}
+
 // After the checks: CLAHE, equalization, or one after the other, on every channel of every page.  luts_out (the entry without a
 // destination): the tile tables go to the caller's memory and no pixel is written.
 int contrast_run(const PageArgs& a, int C, const ContrastSpec& sp, uint8_t* luts_out, void* stream)
 {
     if (a.n_pages == 0) return PRL_OK;
-    const ClaheGeom g = clahe_geometry(a.width, a.height, sp.tiles_x, sp.tiles_y, sp.clip_limit);
     const size_t tiles = sp.clahe ? (size_t)sp.tiles_x * sp.tiles_y : 0;
-    // per page: [tile bins | tile tables | the page's bins | the page's tables], each block of a chunk 256-byte aligned
-    const size_t p_thist = (size_t)C * tiles * 256 * sizeof(unsigned), p_tlut = luts_out ? 0 : (size_t)C * tiles * 256;
-    const size_t p_hist = sp.equalize ? (size_t)C * 256 * sizeof(unsigned) : 0, p_lut = sp.equalize ? (size_t)C * 256 : 0;
-    const int chunk = stage_chunk(a.n_pages, p_thist + p_tlut + p_hist + p_lut + 4 * 256);
+    const ContrastWork cw = contrast_work(C, sp, luts_out != nullptr);
+    const int chunk = stage_chunk(a.n_pages, cw.per_page());
     WorkScope w;
-    int st = w.open(stream, r256(chunk * p_thist) + r256(chunk * p_tlut) + r256(chunk * p_hist) + r256(chunk * p_lut), 0, 0);
+    int st = w.open(stream, cw.bytes(chunk), 0, 0);
     if (st != PRL_OK) return st;
-    const hipStream_t hs = w.stream;
-    unsigned* d_thist = w.scratch<unsigned>();
-    uint8_t* d_tlut = w.scratch() + r256(chunk * p_thist);
-    unsigned* d_hist = reinterpret_cast<unsigned*>(d_tlut + r256(chunk * p_tlut));
-    uint8_t* d_lut = reinterpret_cast<uint8_t*>(d_hist) + r256(chunk * p_hist);
     for (int first = 0; first < a.n_pages; first += chunk) {
         const int n = std::min(chunk, a.n_pages - first);
-        const PageSet s = src_pages(a, first);
-        const PageSetOut d = dst_pages(a, first);
-        if (sp.clahe) {
-            st = clahe_hist_launch(C, s, n, a.width, a.height, g, d_thist, hs);
-            if (st != PRL_OK) return st;
-            uint8_t* tl = luts_out ? luts_out + (size_t)first * C * tiles * 256 : d_tlut;
-            const int n_tiles = (int)((size_t)n * C * tiles);
-            hipLaunchKernelGGL(k_clahe_luts, dim3((unsigned)((n_tiles + 3) / 4)), dim3(kClaheThreads), 0, hs, n_tiles, g.clip, g.lut_scale,
-                               d_thist, tl);
-            PRL_HIP_CHECK(hipGetLastError());
-            if (luts_out) continue;
-            st = clahe_interp_launch(C, s, d, n, a.width, a.height, g, tl, sp.equalize ? d_hist : nullptr, hs);
-            if (st != PRL_OK) return st;
-        } else {
-            st = hist_launch(C, s, n, a.width, a.height, d_hist, hs);
-            if (st != PRL_OK) return st;
-        }
-        if (!sp.equalize) continue;
-        hipLaunchKernelGGL(k_equalize_derive, dim3((unsigned)((n * C + 63) / 64)), dim3(64), 0, hs, n * C, d_hist, d_lut);
-        PRL_HIP_CHECK(hipGetLastError());
-        st = lut_launch(C, C, sp.clahe ? as_source(d) : s, d, n, a.width, a.height, d_lut, (size_t)C * 256, hs);   // (in place after CLAHE)
+        st = contrast_chunk(C, sp, src_pages(a, first), dst_pages(a, first), n, a.width, a.height, cw, chunk, w.scratch(),
+                            luts_out ? luts_out + (size_t)first * C * tiles * 256 : nullptr, w.stream);
         if (st != PRL_OK) return st;
     }
     return PRL_OK;
@@ -419,6 +443,17 @@ ContrastSpec equalize_spec()
 }
 
 }  // namespace
+
+// ---- what prl_internal.h declares of this file: EnhanceLocalContrastByCLAHE(clip_limit, equalize = true) on gray pages inside a
+// caller's workspace (prl::binarizeLocalOtsu, localotsu.hip) ------
+size_t enhance_contrast_work_bytes(int chunk) { return contrast_work(1, clahe_spec(40.0, 8, 8, true), false).bytes(chunk); }
+size_t enhance_contrast_work_per_page() { return contrast_work(1, clahe_spec(40.0, 8, 8, true), false).per_page(); }
+int enhance_contrast_gray_run(double clip_limit, const PageSet& s, const PageSetOut& d, int n, int W, int H, int chunk, uint8_t* work,
+                              hipStream_t hs)
+{
+    const ContrastSpec sp = clahe_spec(clip_limit, 8, 8, true);
+    return contrast_chunk(1, sp, s, d, n, W, H, contrast_work(1, sp, false), chunk, work, nullptr, hs);
+}
 
 }  // namespace prl_hip
 

@@ -143,6 +143,67 @@ inline void ct_find_contours(const uint8_t* map, size_t step, int w, int h, std:
     }
 }
 
+struct CtRect {
+    int32_t x, y, w, h;
+};
+
+// cv::findContours(map, RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), as prl::binarizeLocalOtsu uses it (binarizeLocalOtsu.cpp:100-160): the
+// cv::boundingRect of every contour of at least 3 points (RemoveChildrenContours on a flat hierarchy drops the shorter ones), in
+// discovery order.  Returns the number of contours found, the short ones included.  The raster scan of OpenCV's retrieval mode 0,
+// literally [upstream, from memory]: lnbd is the column of the last border pixel passed in this row (the frame column at its
+// start); a change prev -> p other than 0 -> 1 is either nothing (p != 0 or prev < 1) or a hole start, which moves lnbd to x - 1
+// when prev is a traced pixel and is never traced in this mode; an outer start is skipped while the pixel at lnbd is positive
+// (a traced pixel that is not a right end: the scan is inside that border).  The scan is restated as it is written, not replaced
+// by a topological "outermost component" rule.
+inline int ct_external_rects(const uint8_t* map, size_t step, int w, int h, std::vector<CtRect>* rects)
+{
+    rects->clear();
+    const int pw = w + 2;
+    std::vector<signed char> img((size_t)pw * (h + 2), 0);   // one pixel of background all round
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) img[(size_t)(y + 1) * pw + x + 1] = map[(size_t)y * step + x] != 0;
+    int deltas[16];
+    for (int d = 0; d < 16; ++d) deltas[d] = kCtDy[d & 7] * pw + kCtDx[d & 7];
+    std::vector<CtPoint> pts;
+    int found = 0;
+    for (int y = 1; y <= h; ++y) {
+        signed char* row = img.data() + (size_t)y * pw;
+        int prev = 0, lnbd = 0;
+        for (int x = 1; x <= w; ++x) {
+            int p = row[x];
+            if (p == prev) continue;
+            bool start = true;
+            if (!(prev == 0 && p == 1)) {
+                if (p != 0 || prev < 1) {
+                    start = false;
+                } else {
+                    if (prev & -2) lnbd = x - 1;
+                    start = false;   // a hole start: not traced in this mode
+                }
+            } else if (row[lnbd] > 0) {
+                start = false;
+            }
+            if (start) {
+                pts.clear();
+                ct_trace(row + x, deltas, false, CtPoint{x - 1, y - 1}, &pts);
+                ++found;
+                if (pts.size() >= 3) {
+                    int x0 = pts[0].x, x1 = x0, y0 = pts[0].y, y1 = y0;
+                    for (const CtPoint& q : pts) {
+                        x0 = std::min(x0, q.x); x1 = std::max(x1, q.x);
+                        y0 = std::min(y0, q.y); y1 = std::max(y1, q.y);
+                    }
+                    rects->push_back(CtRect{x0, y0, x1 - x0 + 1, y1 - y0 + 1});
+                }
+                p = row[x];
+            }
+            prev = p;
+            if (prev & -2) lnbd = x;
+        }
+    }
+    return found;
+}
+
 // cv::approxPolyDP(src, dst, eps, closed = true) on integer points; dst has room for n points; returns the new count.
 inline int ct_approx_closed(const CtPoint* src, int n, double eps, CtPoint* dst)
 {

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "ppht_plan.h"
+#include "prl_device_math.h"
 #include "prl_internal.h"
 
 namespace prl_hip {
@@ -61,27 +62,7 @@ __global__ void k_otsu(const unsigned* __restrict__ hist, int width, int height,
 {
     const int page = blockIdx.x * blockDim.x + threadIdx.x;
     if (page >= n_pages) return;
-    const unsigned* h = hist + (size_t)page * 256;
-    double mu = 0;
-    const double scale = 1. / ((double)width * height);
-    for (int i = 0; i < 256; ++i) mu += i * (double)h[i];
-    mu *= scale;
-    double mu1 = 0, q1 = 0, max_sigma = 0, max_val = 0;
-    for (int i = 0; i < 256; ++i) {
-        const double p_i = h[i] * scale;
-        mu1 *= q1;
-        q1 += p_i;
-        const double q2 = 1. - q1;
-        if (fmin(q1, q2) < (double)FLT_EPSILON || fmax(q1, q2) > 1. - (double)FLT_EPSILON) continue;
-        mu1 = (mu1 + i * p_i) / q1;
-        const double mu2 = (mu - q1 * mu1) / q2;
-        const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
-        if (sigma > max_sigma) {
-            max_sigma = sigma;
-            max_val = i;
-        }
-    }
-    thr[page] = (int)max_val;
+    thr[page] = otsu_scan(hist + (size_t)page * 256, 1. / ((double)width * height));   // (prl_device_math.h)
 }
 
 // ---- HoughLinesP stage 1 -------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 // imageLibCommon.h - the part of PRLib's src/imageLibCommon.h that exists here: EnhanceLocalContrastByCLAHE (:151,
-// imageLibCommon.cpp:327-395), declared in the global namespace with the reference's signature, and the two OpenCV functions it is
+// imageLibCommon.cpp:327-395) and CannyEdgeDetection (imageLibCommon.cpp:244-324), declared in the global namespace with the reference's signature, and the two OpenCV functions it is
 // made of as extensions in namespace prl.  Implemented in prl_host.cpp over the C ABI (clahe.hip; the arithmetic is stated in
 // prl_hip.h, "contrast").  The header's other helpers are not provided.
 #pragma once
@@ -13,6 +13,15 @@
 // side above 32768 (documented deviations: cv::CLAHE also takes 16-bit images).  outputImage may be inputImage: the result is a new
 // continuous Mat of the input's type, and the input's pixels are never written.
 CV_EXPORTS void EnhanceLocalContrastByCLAHE(cv::Mat& inputImage, cv::Mat& outputImage, double CLAHEClipLimit, bool equalizeHistFlag);
+
+// imageLibCommon.cpp:244-324 on an 8-bit image of 1 to 4 channels: per channel the 8-bit cv::GaussianBlur(size x size, sigma 0), the
+// Otsu value t, cv::Canny(lower * upper * t, upper * t), the 3 x 3 closing (CannyMorphIters > 0) or opening (< 0); the channels
+// OR-ed into resultCanny, a new CV_8UC1 Mat (edgedet.hip; prl_hip.h, "CannyEdgeDetection").  std::invalid_argument with the
+// reference's messages, in its order: an empty image, GaussianBlurKernelSize < 3, a coefficient outside [0, 1], lower > upper;
+// cv::Exception StsAssert for an even size (cv::GaussianBlur's assertion), StsUnsupportedFormat for a depth other than CV_8U or more
+// than 4 channels, StsBadArg for a size above 255, |CannyMorphIters| above 255 or a side above 32768 (documented deviations).
+CV_EXPORTS void CannyEdgeDetection(cv::Mat& imageToProc, cv::Mat& resultCanny, int GaussianBlurKernelSize, double CannyUpperThresholdCoeff,
+                                   double CannyLowerThresholdCoeff, int CannyMorphIters);
 
 namespace prl {
 

@@ -22,6 +22,7 @@
 //   src/binarizations/binarizeMokji.h:46                   prl::binarizeMokji
 //   src/detectors/blurDetection.h:35                       prl::isBlurred (+ prl::focusMeasures)
 //   src/deblur/basicDeblur.h:32-34                         prl::basicDeblur
+//   src/binarizations/binarizeLocalOtsu.h                  prl::binarizeLocalOtsu
 //   src/warp.h:49-73                                       prl::warpCrop
 //   src/border_detection/autoCrop.h:42-53                  prl::documentContour, prl::autoCrop
 //   src/border_detection/houghLine.h                       prl::findHoughLineContour
@@ -173,6 +174,20 @@ CV_EXPORTS FocusMeasures focusMeasures(const cv::Mat& inputImage, int tengKernel
 // inputImage: the result is a new Mat, and the input's pixels are never written.
 CV_EXPORTS void basicDeblur(const cv::Mat& inputImage, cv::Mat& outputImage, const size_t gaussianKernelSize = 0, const double sigmaX = 9.0,
                             const double sigmaY = 0.0, const double imageWeight = 0.75);
+
+// src/binarizations/binarizeLocalOtsu.h - binarizeLocalOtsu.cpp:37-163 on an 8-bit image of 1, 3 or 4 channels: gray (a colour image
+// through cv::COLOR_RGB2GRAY, as the reference converts it), EnhanceLocalContrastByCLAHE(CLAHEClipLimit, true) when the limit is
+// positive, CannyEdgeDetection, three 3 x 3 dilations, the bounding rectangles of the external contours, and Otsu's threshold of
+// every rectangle painted into a white mask (localotsu.hip; the rules are stated in prl_hip.h, "binarizeLocalOtsu").
+// std::invalid_argument with the reference's messages: an empty image, maxValue outside [0, 255], CannyEdgeDetection's checks
+// (GaussianBlurKernelSize < 3, a coefficient outside [0, 1], lower > upper), and "Contours array is empty" when the edge map has no
+// contour (outputImage then stays as it was).  cv::Exception StsAssert for an even GaussianBlurKernelSize (cv::GaussianBlur's
+// assertion); StsUnsupportedFormat for a depth other than CV_8U or 2 channels; StsBadArg for a kernel size above 255, a NaN clip limit
+// or a side above 32768 (documented deviations).  outputImage may be inputImage: the result is a new CV_8UC1 Mat, and the input's
+// pixels are never written.
+CV_EXPORTS void binarizeLocalOtsu(cv::Mat& inputImage, cv::Mat& outputImage, double maxValue = 255.0, double CLAHEClipLimit = 0.0,
+                                  int GaussianBlurKernelSize = 19, double CannyUpperThresholdCoeff = 0.15,
+                                  double CannyLowerThresholdCoeff = 0.01, int CannyMorphIters = 1);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

@@ -382,6 +382,60 @@ void prl::equalizeHist(const cv::Mat& inputImage, cv::Mat& outputImage)
 
 namespace {
 
+// CannyEdgeDetection's own checks in the reference's order (imageLibCommon.cpp:253-272), then cv::GaussianBlur's assertion
+void canny_edge_checks(int size, double upper, double lower, const char* func, int line)
+{
+    if (size < 3) throw std::invalid_argument("Gaussian blur kernel size is lesser than 3");
+    if (upper < 0 || upper > 1 || upper != upper) throw std::invalid_argument("Canny upper threshold coefficient isn't in range [0;1]");
+    if (lower < 0 || lower > 1 || lower != lower) throw std::invalid_argument("Canny lower threshold coefficient isn't in range [0;1]");
+    if (lower > upper)
+        throw std::invalid_argument("Canny lower threshold coefficient is greater than Canny upper threshold coefficient");
+    if (size % 2 != 1)
+        fail_cv(cv::Error::StsAssert, "ksize.width > 0 && ksize.width % 2 == 1 && ksize.height > 0 && ksize.height % 2 == 1", func, line);
+}
+
+}  // namespace
+
+void CannyEdgeDetection(cv::Mat& imageToProc, cv::Mat& resultCanny, int GaussianBlurKernelSize, double CannyUpperThresholdCoeff,
+                        double CannyLowerThresholdCoeff, int CannyMorphIters)
+{
+    if (imageToProc.empty()) throw std::invalid_argument("Image for histograms extraction is empty");
+    canny_edge_checks(GaussianBlurKernelSize, CannyUpperThresholdCoeff, CannyLowerThresholdCoeff, __func__, __LINE__);
+    if (imageToProc.depth() != CV_8U || imageToProc.channels() > 4)
+        PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "CannyEdgeDetection: 8-bit images of 1..4 channels only");   // documented deviation
+    if (GaussianBlurKernelSize > PRL_GAUSS_MAX_SIDE) PRL_FAIL_CV(cv::Error::StsBadArg, "CannyEdgeDetection: kernel sizes up to 255 only");
+    cv::Mat result(imageToProc.rows, imageToProc.cols, CV_8UC1);
+    const int st = prl_hip_canny_edge_detection_host(imageToProc.channels(), GaussianBlurKernelSize, CannyUpperThresholdCoeff,
+                                                     CannyLowerThresholdCoeff, CannyMorphIters, imageToProc.data, imageToProc.step,
+                                                     imageToProc.cols, imageToProc.rows, result.data, result.step);
+    if (st != PRL_OK) raise(st);
+    resultCanny = result;
+}
+
+// binarizeLocalOtsu.cpp:37-163 in the reference's statement order: its two checks, the gray conversion (cv::cvtColor rejects two
+// channels), CannyEdgeDetection's checks, and RemoveChildrenContours' exception for an edge map without contours.
+void prl::binarizeLocalOtsu(cv::Mat& inputImage, cv::Mat& outputImage, double maxValue, double CLAHEClipLimit, int GaussianBlurKernelSize,
+                            double CannyUpperThresholdCoeff, double CannyLowerThresholdCoeff, int CannyMorphIters)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image for binarization is empty");
+    if (!(maxValue >= 0 && maxValue <= 255)) throw std::invalid_argument("Max value must be in range [0; 255]");
+    if (inputImage.depth() != CV_8U) PRL_FAIL_CV(cv::Error::StsUnsupportedFormat, "prl: 8-bit images only");
+    const int cn = inputImage.channels();
+    if (cn != 1 && cn != 3 && cn != 4) raise(PRL_ERR_BAD_CHANNELS);
+    canny_edge_checks(GaussianBlurKernelSize, CannyUpperThresholdCoeff, CannyLowerThresholdCoeff, __func__, __LINE__);
+    if (GaussianBlurKernelSize > PRL_GAUSS_MAX_SIDE) PRL_FAIL_CV(cv::Error::StsBadArg, "prl::binarizeLocalOtsu: kernel sizes up to 255 only");
+    cv::Mat result(inputImage.rows, inputImage.cols, CV_8UC1);
+    int32_t found = 0, kept = 0;
+    const int st = prl_hip_binarize_local_otsu_host(cn, maxValue, CLAHEClipLimit, GaussianBlurKernelSize, CannyUpperThresholdCoeff,
+                                                    CannyLowerThresholdCoeff, CannyMorphIters, inputImage.data, inputImage.step,
+                                                    inputImage.cols, inputImage.rows, result.data, result.step, &found, &kept);
+    if (st != PRL_OK) raise(st);
+    if (found == 0) throw std::invalid_argument("Contours array is empty");   // RemoveChildrenContours, imageLibCommon.cpp:643-646
+    outputImage = result;
+}
+
+namespace {
+
 constexpr int kAdaptiveMaxBlock = 255;   // prl_hip.h: block_size 3 .. 255
 
 // cv::medianBlur's own checks ([upstream] OpenCV >= 4), as prl::denoiseSaltPepper states them

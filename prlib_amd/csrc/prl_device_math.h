@@ -6,6 +6,8 @@
 // SURVEY.md Appendix B.
 #pragma once
 
+#include <cfloat>
+
 #include <hip/hip_runtime.h>
 
 #include "prl_internal.h"
@@ -97,6 +99,31 @@ __device__ __forceinline__ unsigned sat_u8_literal(double T)
     const double r = rint(T);
     if (!(r >= -2147483648.0 && r <= 2147483647.0)) return 0u;
     return r < 0.0 ? 0u : (r > 255.0 ? 255u : (unsigned)r);
+}
+
+// getThreshVal_Otsu_8u [upstream]: the float64 scan over the 256 bins h of `1 / scale` pixels (ppht.hip: a page; localotsu.hip: a
+// rectangle).  h may live in LDS.
+__device__ __forceinline__ int otsu_scan(const unsigned* h, double scale)
+{
+    double mu = 0;
+    for (int i = 0; i < 256; ++i) mu += i * (double)h[i];
+    mu *= scale;
+    double mu1 = 0, q1 = 0, max_sigma = 0, max_val = 0;
+    for (int i = 0; i < 256; ++i) {
+        const double p_i = h[i] * scale;
+        mu1 *= q1;
+        q1 += p_i;
+        const double q2 = 1. - q1;
+        if (fmin(q1, q2) < (double)FLT_EPSILON || fmax(q1, q2) > 1. - (double)FLT_EPSILON) continue;
+        mu1 = (mu1 + i * p_i) / q1;
+        const double mu2 = (mu - q1 * mu1) / q2;
+        const double sigma = q1 * q2 * (mu1 - mu2) * (mu1 - mu2);
+        if (sigma > max_sigma) {
+            max_sigma = sigma;
+            max_val = i;
+        }
+    }
+    return (int)max_val;
 }
 
 // in(rect) > T8  — binarizeSauvola.cpp:122

@@ -547,8 +547,39 @@ int resized_dst_ok(const PageArgs& a, int channels, int out_width, int out_heigh
 size_t canny_work_bytes(int n, int W, int H);
 size_t canny_pinned_bytes(int n);
 int canny_pages_per_chunk(int n_pages, int W, int H, size_t extra_per_page);
+// d_page_t (device, n ints in 0 .. 255) with d_lut (device, 256 pairs): page i takes the thresholds d_lut[2 t], d_lut[2 t + 1] of its
+// t = d_page_t[i] instead of low / high (CannyEdgeDetection: the pair follows the page's Otsu value, which never leaves the device)
 int canny_run(int W, int H, int low, int high, const PageSet& src, const PageSetOut& dst, int n, uint8_t* work, unsigned* h_flags,
-              hipStream_t stream, int channels = 1);
+              hipStream_t stream, int channels = 1, const int* d_lut = nullptr, const int* d_page_t = nullptr);
+// lut[2 t], lut[2 t + 1] = cv::Canny's integer pair for threshold2 = upper_coeff * t, threshold1 = lower_coeff * threshold2, t = 0 .. 255
+void canny_threshold_table(double upper_coeff, double lower_coeff, int* lut);
+
+// ---- the 8-bit separable filter (blur8.hip): wx / wy are nx / ny 8.8 weights in tap order, each side summing to at most 256; n
+// pages of 1..4 channels, source and destination distinct; needs no workspace; enqueues only ----------
+int sep_filter_u8_batch(const uint16_t* wx, int nx, const uint16_t* wy, int ny, const PageArgs& a, int channels, hipStream_t stream);
+
+// ---- CannyEdgeDetection (edgedet.hip; imageLibCommon.cpp:244-324) of n pages (a chunk) of C channels into 0 / 255 maps.  work:
+// ced_work_bytes; small: ced_small_bytes; h_flags: pinned, ced_pinned_bytes.  Synchronises the stream (caller holds ctx->mu).
+// ced_pages_per_chunk: the pages a chunk takes when a page costs extra_per_page bytes beside the stage's own ------
+struct CedSpec {
+    int size;                          // GaussianBlurKernelSize
+    double upper_coeff, lower_coeff;   // CannyUpperThresholdCoeff, CannyLowerThresholdCoeff
+    int iterations;                    // CannyMorphIters
+};
+int ced_spec_check(const CedSpec& sp);   // 0, or the number of the reference's check that fails (5: an even size)
+int ced_pages_per_chunk(const CedSpec& sp, int n_pages, int W, int H, int C, size_t extra_per_page);
+size_t ced_work_bytes(const CedSpec& sp, int n, int W, int H, int C);
+size_t ced_small_bytes(int n, int C);
+size_t ced_pinned_bytes(int n, int C);
+int ced_run(const CedSpec& sp, const PageSet& src, const PageSetOut& dst, int n, int W, int H, int C, uint8_t* work, uint8_t* small,
+            unsigned* h_flags, hipStream_t stream);
+
+// ---- EnhanceLocalContrastByCLAHE(clip_limit, equalize = true) on n gray pages inside a caller's workspace (clahe.hip), in place
+// or not; work: enhance_contrast_work_bytes(chunk) for the chunk the n pages are part of; enqueues only ----------
+size_t enhance_contrast_work_bytes(int chunk);
+size_t enhance_contrast_work_per_page();
+int enhance_contrast_gray_run(double clip_limit, const PageSet& src, const PageSetOut& dst, int n, int W, int H, int chunk, uint8_t* work,
+                              hipStream_t stream);
 
 // ---- cv::HoughLines(rho 1, theta pi / 180) (hough.hip): the sizes of a W x H map's transform, per page and rounded to 256 bytes ----
 struct HoughPlan {
