@@ -276,7 +276,17 @@ struct ThinPlan {
     size_t scratch_bytes() const { return 2 * bits_bytes + 2 * flags_bytes + 2 * act_cap; }
 };
 
-ThinPlan thin_plan(int n_pages, int width, int height)
+// What a caller may fix instead of taking the plan's and the loop's own choice.  The defaults are the product's behaviour; only the
+// test-hooks entry at the end of this file passes anything else.
+struct ThinOpts {
+    int rps = 0;         // rows per segment (0: from the batch size, or PRL_THIN_RPS)
+    int wpb = 0;         // wavefronts per workgroup of k_thin_pass (0: PRL_THIN_WPB)
+    int n_passes = -1;   // -1: until every page has converged; n >= 0: exactly n passes, then unpack the plane the last one wrote
+    unsigned char* d_act = nullptr;   // out: the activity bytes the last pass wrote, one per page x segment x strip
+    unsigned* d_done = nullptr;       // out: the pages' flags after the last k_thin_endpass
+};
+
+ThinPlan thin_plan(int n_pages, int width, int height, const ThinOpts& o = {})
 {
     ThinPlan t{};
     t.wpr = (width + 31) / 32;
@@ -287,6 +297,7 @@ ThinPlan thin_plan(int n_pages, int width, int height)
     t.rps = 256;  // measured (16 A4 pages): 32 rows 31 us per pass, 16: 26, 8: 26, 4: 31
     while (t.rps > 16 && (long long)n_pages * t.n_strips * ((height + t.rps - 1) / t.rps) < 16384) t.rps /= 2;
     if (env_knobs().thin_rps) t.rps = env_knobs().thin_rps;
+    if (o.rps) t.rps = o.rps;
     t.n_segs = (height + t.rps - 1) / t.rps;
     t.tw = (unsigned long long)n_pages * t.n_strips * t.n_segs;
     t.act_cap = r256((size_t)t.tw);  // one activity byte per tile and pass parity
@@ -295,7 +306,7 @@ ThinPlan thin_plan(int n_pages, int width, int height)
 
 // one chunk: the planes of its pages at the head of scratch, the flag readback through pinned memory
 int thin_chunk(const WorkScope& w, const ThinPlan& t, int method, int n_pages, const PageSet& ps, int width, int height,
-               const PageSetOut& pd, bool invert_input)
+               const PageSetOut& pd, bool invert_input, const ThinOpts& o = {})
 {
     const hipStream_t s = w.stream;
     auto* A = w.scratch<unsigned>();
@@ -316,34 +327,75 @@ int thin_chunk(const WorkScope& w, const ThinPlan& t, int method, int n_pages, c
     // 2-pixel diagonal stroke erodes from its ends only, about a row per pass (max(W,H)+2 was an unproven bound
     // that returned a non-converged plane).  Every effective pass removes at least one pixel, so the loop ends.
     int group = 4;  // passes per host check, doubled each time (a pass over converged pages / idle tiles is nearly free)
-    const unsigned wpb = (unsigned)env_knobs().thin_wpb;
+    const unsigned wpb = (unsigned)(o.wpb ? o.wpb : env_knobs().thin_wpb);
     const dim3 gp((unsigned)((t.tw + wpb - 1) / wpb)), bp(64 * wpb);  // short wavefronts: 4 per workgroup measured best (26.1 vs 28.4 us)
     // Passes alternate A -> B -> A.  The pass that finds a page unchanged has just written a copy of its input, so
-    // from then on BOTH buffers hold that page's final plane (later passes skip it): k_thin_unpack can always read A.
-    for (int pass = 0;;) {
-        for (int gidx = 0; gidx < group; ++gidx, ++pass) {
-            const unsigned* in = (pass & 1) ? B : A;
-            unsigned* out = (pass & 1) ? A : B;
-            const unsigned char* act_prev = (pass & 1) ? act1 : act0;
-            unsigned char* act_cur = (pass & 1) ? act0 : act1;
-            if (method == PRL_THIN_ZHANGSUEN)
-                hipLaunchKernelGGL(k_thin_pass<0>, gp, bp, 0, s, in, out, t.plane_words, t.wpr, width, height, t.n_strips,
-                                   t.n_segs, t.rps, (unsigned)t.tw, changed, done, act_prev, act_cur);
-            else
-                hipLaunchKernelGGL(k_thin_pass<1>, gp, bp, 0, s, in, out, t.plane_words, t.wpr, width, height, t.n_strips,
-                                   t.n_segs, t.rps, (unsigned)t.tw, changed, done, act_prev, act_cur);
-            PRL_HIP_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(k_thin_endpass, dim3((n_pages + 255) / 256), dim3(256), 0, s, changed, done, n_pages);
-            PRL_HIP_CHECK(hipGetLastError());
+    // from then on BOTH buffers hold that page's final plane (later passes skip it): after the even number of passes the loop
+    // below makes, k_thin_unpack reads A.
+    auto one_pass = [&](int pass) -> int {
+        const unsigned* in = (pass & 1) ? B : A;
+        unsigned* out = (pass & 1) ? A : B;
+        const unsigned char* act_prev = (pass & 1) ? act1 : act0;
+        unsigned char* act_cur = (pass & 1) ? act0 : act1;
+        if (method == PRL_THIN_ZHANGSUEN)
+            hipLaunchKernelGGL(k_thin_pass<0>, gp, bp, 0, s, in, out, t.plane_words, t.wpr, width, height, t.n_strips,
+                               t.n_segs, t.rps, (unsigned)t.tw, changed, done, act_prev, act_cur);
+        else
+            hipLaunchKernelGGL(k_thin_pass<1>, gp, bp, 0, s, in, out, t.plane_words, t.wpr, width, height, t.n_strips,
+                               t.n_segs, t.rps, (unsigned)t.tw, changed, done, act_prev, act_cur);
+        PRL_HIP_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_thin_endpass, dim3((n_pages + 255) / 256), dim3(256), 0, s, changed, done, n_pages);
+        PRL_HIP_CHECK(hipGetLastError());
+        return PRL_OK;
+    };
+    int pass = 0, st;
+    if (o.n_passes >= 0) {   // (test hooks) a fixed count, converged or not
+        for (; pass < o.n_passes; ++pass)
+            if ((st = one_pass(pass)) != PRL_OK) return st;
+    } else {
+        for (;;) {
+            for (int gidx = 0; gidx < group; ++gidx, ++pass)
+                if ((st = one_pass(pass)) != PRL_OK) return st;
+            PRL_HIP_CHECK(hipMemcpyAsync(h_done, done, sizeof(unsigned) * (size_t)n_pages, hipMemcpyDeviceToHost, s));
+            PRL_HIP_CHECK(hipStreamSynchronize(s));
+            if (std::all_of(h_done, h_done + n_pages, [](unsigned v) { return v != 0; })) break;
+            group = std::min(group * 2, 32);
         }
-        PRL_HIP_CHECK(hipMemcpyAsync(h_done, done, sizeof(unsigned) * (size_t)n_pages, hipMemcpyDeviceToHost, s));
-        PRL_HIP_CHECK(hipStreamSynchronize(s));
-        if (std::all_of(h_done, h_done + n_pages, [](unsigned v) { return v != 0; })) break;
-        group = std::min(group * 2, 32);
     }
+    // pass `pass - 1` wrote B when it was even, A when odd; a skipped tile, and a page that was final already, is the same in both
+    const unsigned* last = (pass & 1) ? B : A;
     const dim3 gu((unsigned)(((size_t)(t.wpr + 1) * height + 255) / 256), n_pages);  // one thread per aligned 32-byte block
-    hipLaunchKernelGGL(k_thin_unpack, gu, dim3(256), 0, s, A, t.plane_words, t.wpr, pd, width, height);
+    hipLaunchKernelGGL(k_thin_unpack, gu, dim3(256), 0, s, last, t.plane_words, t.wpr, pd, width, height);
     PRL_HIP_CHECK(hipGetLastError());
+    if (o.d_act) PRL_HIP_CHECK(hipMemcpyAsync(o.d_act, (pass & 1) ? act1 : act0, (size_t)t.tw, hipMemcpyDeviceToDevice, s));
+    if (o.d_done) PRL_HIP_CHECK(hipMemcpyAsync(o.d_done, done, sizeof(unsigned) * (size_t)n_pages, hipMemcpyDeviceToDevice, s));
+    return PRL_OK;
+}
+
+// The pages per chunk of a call (the page index sits in a grid dimension limited to 65535)
+int thin_pages_per_chunk(int n_pages) { return stage_chunk(n_pages, 0, 0, 32768); }
+
+// A batch runs as full chunks and one shorter last chunk; each has the geometry of a batch of that many pages (fewer pages may mean
+// shorter row segments, hence more activity bytes), and both are refused or sized here, before anything is allocated or enqueued.
+// geom (test hooks): wpr, n_strips, rps, n_segs of the full chunk.
+int thin_run(int method, int n_pages, const PageSet& ps, int width, int height, const PageSetOut& pd, void* stream, bool invert_input,
+             const ThinOpts& o, int* geom)
+{
+    WorkScope w;
+    int st = w.lock(stream);
+    if (st != PRL_OK || n_pages <= 0) return st;
+    const int chunk = thin_pages_per_chunk(n_pages), last = n_pages % chunk ? n_pages % chunk : chunk;
+    const ThinPlan full = thin_plan(chunk, width, height, o), tail = thin_plan(last, width, height, o);
+    if (full.plane_words >= 0x7fffff00ull) return PRL_ERR_BAD_ARG;  // kernels index a page's words with 32 bits
+    if (full.tw >= 0xfffffff0ull || tail.tw >= 0xfffffff0ull) return PRL_ERR_BAD_ARG;
+    if (geom) geom[0] = full.wpr, geom[1] = full.n_strips, geom[2] = full.rps, geom[3] = full.n_segs;
+    st = w.grow(std::max(full.scratch_bytes(), tail.scratch_bytes()), 0, sizeof(unsigned) * (size_t)chunk);
+    if (st != PRL_OK) return st;
+    for (int first = 0; first < n_pages; first += chunk) {
+        const int cnt = std::min(chunk, n_pages - first);
+        st = thin_chunk(w, cnt == chunk ? full : tail, method, cnt, pages_from(ps, first), width, height, pages_from(pd, first), invert_input, o);
+        if (st != PRL_OK) return st;
+    }
     return PRL_OK;
 }
 }  // namespace
@@ -351,24 +403,7 @@ int thin_chunk(const WorkScope& w, const ThinPlan& t, int method, int n_pages, c
 int thin_batch_device(int method, int n_pages, const PageSet& ps, int width, int height, const PageSetOut& pd, void* stream,
                       bool invert_input)
 {
-    WorkScope w;
-    int st = w.lock(stream);
-    if (st != PRL_OK || n_pages <= 0) return st;
-    // The page index sits in a grid dimension limited to 65535.  A batch runs as full chunks and one shorter last chunk; each
-    // has the geometry of a batch of that many pages (fewer pages may mean shorter row segments, hence more activity bytes),
-    // and both are refused or sized here, before anything is allocated or enqueued.
-    const int chunk = stage_chunk(n_pages, 0, 0, 32768), last = n_pages % chunk ? n_pages % chunk : chunk;
-    const ThinPlan full = thin_plan(chunk, width, height), tail = thin_plan(last, width, height);
-    if (full.plane_words >= 0x7fffff00ull) return PRL_ERR_BAD_ARG;  // kernels index a page's words with 32 bits
-    if (full.tw >= 0xfffffff0ull || tail.tw >= 0xfffffff0ull) return PRL_ERR_BAD_ARG;
-    st = w.grow(std::max(full.scratch_bytes(), tail.scratch_bytes()), 0, sizeof(unsigned) * (size_t)chunk);
-    if (st != PRL_OK) return st;
-    for (int first = 0; first < n_pages; first += chunk) {
-        const int cnt = std::min(chunk, n_pages - first);
-        st = thin_chunk(w, cnt == chunk ? full : tail, method, cnt, pages_from(ps, first), width, height, pages_from(pd, first), invert_input);
-        if (st != PRL_OK) return st;
-    }
-    return PRL_OK;
+    return thin_run(method, n_pages, ps, width, height, pd, stream, invert_input, ThinOpts{}, nullptr);
 }
 }  // namespace prl_hip
 
@@ -387,6 +422,31 @@ int prl_hip_thin_batch_device(int method, int n_pages, const uint8_t* d_src, siz
     if (n_pages == 0) return PRL_OK;
     return thin_batch_device(method, n_pages, src_pages(a, 0), width, height, dst_pages(a, 0), stream, false);
 }
+
+#ifdef PRL_TEST_HOOKS
+// libprlib_hip_testhooks.so only: the product's own pack, pass loop and unpack (thin_run above) with the pass count and the tile
+// geometry fixed by the caller.  n_passes >= 0: exactly that many passes, whether or not the pages converge, and the plane the last
+// one wrote is unpacked (0: pack and unpack only); -1: the product's loop.  rps / wpb: rows per segment (>= 4) and wavefronts per
+// workgroup (1 .. 4) of k_thin_pass, 0: what the product takes.  d_act (device, n_pages x n_segs x n_strips bytes, may be null): the
+// activity bytes the last pass wrote, 0 for a tile it skipped or left unchanged (a page that had converged before that pass keeps
+// older bytes); d_done (device, n_pages u32, may be null): the flags after the last pass; geom (host): wpr, n_strips, rps, n_segs.
+// The pages of one chunk at most.
+int prl_hip_internal_thin_passes(int method, int n_pages, const uint8_t* d_src, size_t src_page_stride, size_t src_step, int width,
+                                 int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step, int n_passes, int invert_input,
+                                 int rps, int wpb, unsigned char* d_act, unsigned* d_done, int* geom, void* stream)
+{
+    const PageArgs a{n_pages, d_src, src_page_stride, src_step, width, height, d_dst, dst_page_stride, dst_step};
+    int st = pages_nonempty(a);
+    if (st != PRL_OK) return st;
+    if (method != PRL_THIN_ZHANGSUEN && method != PRL_THIN_GUOHALL) return PRL_ERR_BAD_ARG;
+    if ((st = pages_rows_ok(a, 1, 1, true)) != PRL_OK) return st;
+    if (n_pages <= 0 || n_pages > thin_pages_per_chunk(n_pages) || n_passes < -1 || !geom) return PRL_ERR_BAD_ARG;
+    if ((rps != 0 && rps < 4) || wpb < 0 || wpb > 4) return PRL_ERR_BAD_ARG;
+    ThinOpts o;
+    o.rps = rps, o.wpb = wpb, o.n_passes = n_passes, o.d_act = d_act, o.d_done = d_done;
+    return thin_run(method, n_pages, src_pages(a, 0), width, height, dst_pages(a, 0), stream, invert_input != 0, o, geom);
+}
+#endif
 
 int prl_hip_thin_host(int method, const uint8_t* src, size_t src_step, int width, int height, uint8_t* dst, size_t dst_step)
 {

@@ -103,7 +103,9 @@ def test_thinning_many_passes_on_a_multi_tile_page(prl, oracle, cuda_device, met
     yy, xx = np.mgrid[0:h, 0:w]
     for cy, cx, r in [(120, 300, 60), (400, 1900, 45), (600, 1925, 30), (350, 4200, 80), (20, 2500, 25)]:
         img[(yy - cy) ** 2 + (xx - cx) ** 2 <= r * r] = 255
-    img[500:560, 3000:3600] = 255                      # a bar across a strip boundary
+    img[500:560, 3000:3600] = 255                      # a thick bar inside the second strip (columns 1920 .. 3839)
+    img[230:270, 1700:2150] = 255                      # bars across the strip boundaries at x = 1920 and x = 3840
+    img[610:650, 3700:3990] = 255
     img[rng.random((h, w)) < 0.001] = 255
     fn = prl.thinZhangSuen if method == 0 else prl.thinGuoHall
     got = fn(torch.from_numpy(img).to(cuda_device)).cpu().numpy()
