@@ -914,6 +914,46 @@ int prl_hip_canny_edge_detection_host(int channels, int blur_size, double upper_
 int prl_hip_external_rects(const uint8_t* map, size_t step, int width, int height, int32_t* rects, int max_rects, int* n_found,
                            int* n_kept);
 
+/*
+ * Rule R: what the scan above gives, said without a scan (components.h, components.hip; the evidence: DESIGN.md §4.4p).
+ * Foreground is every non-zero byte.  Foreground components are 8-connected, background components 4-connected.  A background
+ * component is OUTER if it holds a pixel of the page's border (the page is thought of as surrounded by background).  A
+ * foreground component's FIRST PIXEL is its smallest y * width + x.  A foreground component is EXTERNAL if its first pixel has
+ * x == 0 or if the pixel to the left of it belongs to an outer background component.  n_found is the number of external
+ * components.  An external component is KEPT unless it is a straight one-pixel line: area == max(bw, bh) and (min(bw, bh) == 1
+ * or bw == bh), a single pixel included (the contours of fewer than 3 points).  The result is the bounding rectangles
+ * (x, y, bw, bh) of the kept components in increasing order of first pixel.  Everything is integer: the device entries below
+ * and prl_hip_external_rects agree byte for byte (tests/test_components_cpu.py pins the equivalence on the host).
+ *
+ * prl_hip_connected_components_batch_device: the foreground components of n_pages maps in device memory, `connectivity` 8 or 4.
+ * d_labels (device, int32, rows labels_step BYTES apart, pages labels_page_stride bytes; NULL: not wanted): 0 for background,
+ * 1 .. K for the page's components in increasing order of first pixel.  n_components (HOST, n_pages values): K of every page.
+ * d_stats (device, NULL: not wanted): five int32 per component - left, top, width, height, area - page after page in label
+ * order, written only if the components of all pages together are at most max_components (else the labels and the counts alone:
+ * call again with room).  Inside, ONE int32 plane per page holds, for every pixel, the smallest linear index of its own-class
+ * component (foreground at `connectivity`, background 4-connected, labelled in the same passes): a union-find per 32 x 32 tile in
+ * LDS, unions across the tile seams by atomic minimum, a flatten pass; a component's number is an ordered prefix count of the
+ * roots.  Every kernel finishes for any input: labels only decrease, and no workgroup waits for another.
+ *
+ * prl_hip_external_rects_batch_device: rule R on n_pages maps in device memory.  n_found, n_kept (HOST, n_pages values each)
+ * and rect_offsets (HOST, n_pages + 1 values: the kept rectangles of page i are [rect_offsets[i], rect_offsets[i + 1])) are
+ * always written; d_rects (device, x, y, width, height each, page after page) only if rect_offsets[n_pages] <= max_rects (the
+ * capacity rule of prl_hip_external_rects: else the counts alone, d_rects untouched).  The total is known only after the last
+ * page: a batch that needs more than one chunk of pages (4 B of labels a pixel against the workspace budget) or more than one
+ * statistics pass (2^20 components) is therefore labelled twice, once for the counts and once to write.
+ *
+ * Both wait for the stream (the counts are host values).  Checked in this order, before any device is touched: PRL_ERR_EMPTY;
+ * PRL_ERR_BAD_ARG (a connectivity other than 4 and 8; a null map or count pointer; negative n_pages; a step below the row bytes;
+ * a side above 32768; a negative capacity, or a positive one with a null array; labels not aligned to 4 bytes).  n_pages == 0
+ * is PRL_OK.
+ */
+int prl_hip_connected_components_batch_device(int n_pages, int connectivity, const uint8_t* d_map, size_t map_page_stride, size_t map_step,
+                                              int width, int height, int32_t* d_labels, size_t labels_page_stride, size_t labels_step,
+                                              int32_t* n_components, int32_t* d_stats, int max_components, void* stream);
+int prl_hip_external_rects_batch_device(int n_pages, const uint8_t* d_map, size_t map_page_stride, size_t map_step, int width, int height,
+                                        int32_t* d_rects, int max_rects, int32_t* rect_offsets, int32_t* n_found, int32_t* n_kept,
+                                        void* stream);
+
 #define PRL_RECT_OTSU_SMALL_AREA 4096   /* a rectangle of at most this many pixels is one wavefront's; a larger one is split */
 
 /*
@@ -944,6 +984,9 @@ int prl_hip_rect_otsu_batch_device(int n_pages, const int32_t* rect_offsets, con
  *   3. CannyEdgeDetection above; 4. cv::dilate 3 x 3, three iterations
  *   5. one read-back of the edge maps; 6. prl_hip_external_rects of each on the host thread pool
  *   7. the rectangles go up; prl_hip_rect_otsu_batch_device's kernels on the gray page of step 2 (not the blurred one)
+ * (steps 5 and 6 on the device - the labels of the maps, rule R's rectangles written where step 7 reads them, only the per-page
+ * counts crossing to the host - are built and give the same bytes, but measured no faster: the test-hooks build selects them with
+ * PRL_HIP_LO_HOST_RECTS=0)
  * n_found / n_kept (host memory, n_pages values each, or NULL): the contours and the rectangles of every page.  A page without
  * contours (n_found == 0) is all 255; the C++ function throws the reference's std::invalid_argument for it.
  * Checked in this order: PRL_ERR_EMPTY; PRL_ERR_BAD_ARG (max_value outside [0, 255]; CannyEdgeDetection's argument checks in its

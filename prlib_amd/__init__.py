@@ -14,6 +14,7 @@ from .mokji import binarizeMokji, cooccurrence, mokjiThreshold, mokjiThresholds 
 from .detectors import focusFromSums, focusMeasures, focusSums  # noqa: F401
 from .deblur import basicDeblur, gaussianBlurF32, gaussianBlurSize, gaussianKernelF32  # noqa: F401
 from .contrast import clahe, claheGeometry, claheLuts, claheTileLut, enhanceLocalContrast, equalizeHist, equalizeHistLut  # noqa: F401
+from .components import connectedComponents  # noqa: F401
 from .localotsu import (binarizeLocalOtsu, cannyEdgeDetection, externalRects, gaussianBlurU8, gaussianKernelU8, rectOtsu,  # noqa: F401
                         sepFilterU8)
 from .thinning import thinGuoHall, thinZhangSuen  # noqa: F401
@@ -34,6 +35,6 @@ from .binarizations import (  # noqa: F401
 __all__ = [
     "binarize", "binarizeSauvola", "binarizeNiblack", "binarizeWolfJolion", "binarizeNICK", "binarizeFeng", "binarizeByLocalVariances", "binarizeByLocalVariancesWithoutFilters",
     "adaptiveThreshold", "binarizeNativeAdaptive", "binarizeAT", "binarizeAGT", "binarizePureAdaptiveGaussian",
-    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "morphology_ex", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "focusSums", "focusMeasures", "focusFromSums", "basicDeblur", "gaussianBlurF32", "gaussianKernelF32", "gaussianBlurSize", "clahe", "claheLuts", "equalizeHist", "enhanceLocalContrast", "claheGeometry", "claheTileLut", "equalizeHistLut", "binarizeLocalOtsu", "cannyEdgeDetection", "externalRects", "gaussianBlurU8", "gaussianKernelU8", "rectOtsu", "sepFilterU8", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize", "resize_pyramid_levels", "find_contours", "approx_poly_closed", "document_quad", "document_quad_finish", "document_contour", "auto_crop", "hough_lines_geometry", "hough_accumulator", "hough_lines", "hough_edges", "hough_line_quad", "hough_line_contour", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
+    "denoise", "denoiseSaltPepper", "nlm_planes", "correctNUIL", "morphologyEx", "morphology_ex", "removeLines", "gammaCorrection", "simpleWhiteBalance", "grayWorldWhiteBalance", "cleanBackgroundToWhite", "histogram", "lut", "binarizeMokji", "mokjiThresholds", "mokjiThreshold", "cooccurrence", "focusSums", "focusMeasures", "focusFromSums", "basicDeblur", "gaussianBlurF32", "gaussianKernelF32", "gaussianBlurSize", "clahe", "claheLuts", "equalizeHist", "enhanceLocalContrast", "claheGeometry", "claheTileLut", "equalizeHistLut", "connectedComponents", "binarizeLocalOtsu", "cannyEdgeDetection", "externalRects", "gaussianBlurU8", "gaussianKernelU8", "rectOtsu", "sepFilterU8", "backgroundNormalization", "deskew", "rotate", "houghp", "findAngle", "findOrientation", "deskew_stats", "warp_crop_size", "perspective_transform", "warp_perspective", "warp_crop", "warp_crop_host", "pyr_down", "pyr_down_size", "canny", "canny_classes", "edge_link", "document_edges", "document_edges_geometry", "resize", "resize_pyramid_levels", "find_contours", "approx_poly_closed", "document_quad", "document_quad_finish", "document_contour", "auto_crop", "hough_lines_geometry", "hough_accumulator", "hough_lines", "hough_edges", "hough_line_quad", "hough_line_contour", "thinZhangSuen", "thinGuoHall", "cvtColorBGR2GRAY", "cvtColorGRAY2BGR", "bitwise_not", "process_pages", "process_pages_host", "make_params", "default_params", "geometry", "last_stats", "morph", "set_exec_mode", "set_literal_page_budget", "set_deferred_completion", "finish", "binarize_pages_host", "PinnedPages",
     "SAUVOLA", "NIBLACK", "WOLFJOLION", "NICK", "FENG",
 ]

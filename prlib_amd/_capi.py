@@ -87,7 +87,7 @@ EXPORTED_SYMBOLS = [
     "prl_hip_gaussian_kernel_u8", "prl_hip_sep_filter_u8_batch_device", "prl_hip_gaussian_blur_u8_batch_device",
     "prl_hip_gaussian_blur_u8_host", "prl_hip_canny_edge_detection_batch_device", "prl_hip_canny_edge_detection_host",
     "prl_hip_external_rects", "prl_hip_rect_otsu_batch_device", "prl_hip_binarize_local_otsu_batch_device",
-    "prl_hip_binarize_local_otsu_host",
+    "prl_hip_binarize_local_otsu_host", "prl_hip_connected_components_batch_device", "prl_hip_external_rects_batch_device",
 ]
 
 
@@ -313,6 +313,8 @@ def lib() -> C.CDLL:
         L.prl_hip_rect_otsu_batch_device.argtypes = [i, vp, vp, d, vp, sz, sz, i, i, vp, sz, sz, vp, vp]
         L.prl_hip_binarize_local_otsu_batch_device.argtypes = [i, i, d, d, i, d, d, i, vp, sz, sz, i, i, vp, sz, sz, vp, vp, vp]
         L.prl_hip_binarize_local_otsu_host.argtypes = [i, d, d, i, d, d, i, vp, sz, i, i, vp, sz, vp, vp]
+        L.prl_hip_connected_components_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp, vp, i, vp]
+        L.prl_hip_external_rects_batch_device.argtypes = [i, vp, sz, sz, i, i, vp, i, vp, vp, vp, vp]
         _lib = L
     return _lib
 

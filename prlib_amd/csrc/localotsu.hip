@@ -17,7 +17,9 @@
 //
 // The composed call: gray (COLOR_RGB2GRAY for colour pages), EnhanceLocalContrastByCLAHE (clahe.hip), CannyEdgeDetection
 // (edgedet.hip), a 7 x 7 dilation (three iterations of 3 x 3; gmorph.hip), ONE read-back of the edge maps per chunk, the external
-// bounding rectangles on the host thread pool (contour.h), their upload, and the kernels above.
+// bounding rectangles on the host thread pool (contour.h), their upload, and the kernels above.  The same rectangles from the
+// device (components.hip: only the per-page counts cross to the host) measured no faster on whole calls (profiles/r24/INDEX.md):
+// that path is kept behind the hooks build's PRL_HIP_LO_HOST_RECTS=0.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -249,25 +251,121 @@ int lo_checks(const PageArgs& a, int channels, const LoSpec& sp, bool batch)
     return pages_overlap_ok(a, channels, 1, false);
 }
 
+// Steps 5 to 7 of a chunk with the rectangles from the host scan (contour.h), the call's path.  One read-back of the
+// maps `D`, ct_external_rects per page on the host pool, the upload, kRectChunk rectangles a pass.
+int lo_rects_host(const WorkScope& w, const uint8_t* D, size_t plane, int n, int W, int H, RectJob j, uint8_t* stage_work, size_t off_bytes,
+                  const PageSet& gray, const PageSetOut& dst, int32_t* n_found, int32_t* n_kept)
+{
+    const hipStream_t hs = w.stream;
+    uint8_t* h_maps = w.pinned();
+    PRL_HIP_CHECK(hipMemcpyAsync(h_maps, D, plane * (size_t)n, hipMemcpyDeviceToHost, hs));
+    PRL_HIP_CHECK(hipStreamSynchronize(hs));
+    std::vector<std::vector<CtRect>> rects((size_t)n);
+    host_pool_for(n, [&](int i) {
+        const int found = ct_external_rects(h_maps + plane * (size_t)i, (size_t)W, W, H, &rects[(size_t)i]);
+        if (n_found) n_found[i] = found;
+        if (n_kept) n_kept[i] = (int32_t)rects[(size_t)i].size();
+    });
+    std::vector<int32_t> offsets((size_t)n + 1, 0), flat;
+    for (int i = 0; i < n; ++i) {
+        for (const CtRect& r : rects[(size_t)i]) flat.insert(flat.end(), {r.x, r.y, r.w, r.h});
+        if (flat.size() / 4 > 0x7fffffffu) return bad_arg("binarizeLocalOtsu: too many rectangles");
+        offsets[(size_t)i + 1] = (int32_t)(flat.size() / 4);
+    }
+    const int total = offsets[(size_t)n];
+    int32_t* d_off = w.small<int32_t>();
+    int32_t* d_rects = reinterpret_cast<int32_t*>(stage_work);
+    uint8_t* pass_work = stage_work + r256((size_t)kRectChunk * 16);
+    PRL_HIP_CHECK(hipMemcpyAsync(d_off, offsets.data(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, hs));
+    j.rects = d_rects; j.offsets = d_off;
+    j.thr = reinterpret_cast<int32_t*>(w.small() + off_bytes);
+    int st;
+    for (int r0 = 0; r0 < total; r0 += kRectChunk) {
+        const int r1 = std::min(total, r0 + kRectChunk);
+        PRL_HIP_CHECK(hipMemcpyAsync(d_rects, flat.data() + 4 * (size_t)r0, (size_t)(r1 - r0) * 16, hipMemcpyHostToDevice, hs));
+        j.rect_base = r0;
+        j.thr_base = r0;
+        if ((st = rect_pass(j, r0, r1, pass_work, gray, dst, hs)) != PRL_OK) return st;
+    }
+    PRL_HIP_CHECK(hipStreamSynchronize(hs));   // (`flat` and `offsets` end with this scope)
+    return PRL_OK;
+}
+
+// Steps 5 to 7 of a chunk on the device (components.hip): the labels of the maps, rule R's rectangles a statistics pass at a time
+// where rect_pass reads them; the host sees the per-page counts only, from which it lays out the pass's offsets.  The same bytes
+// as the host path, no faster: behind the hooks build's PRL_HIP_LO_HOST_RECTS=0, so that a test and the benchmark can run both.
+int lo_rects_device(const WorkScope& w, const PageSet& maps, int n, int W, int H, RectJob j, uint8_t* cc_work, uint8_t* pass_work,
+                    const PageSet& gray, const PageSetOut& dst, int32_t* n_found, int32_t* n_kept)
+{
+    const hipStream_t hs = w.stream;
+    const size_t off_bytes = r256(((size_t)n + 1) * sizeof(int32_t));
+    CcRun r;
+    r.maps = maps;
+    r.n = n; r.W = W; r.H = H;
+    r.work = cc_work;
+    r.small = w.small() + off_bytes + r256((size_t)kRectChunk * sizeof(int32_t));
+    r.pinned = w.pinned<int32_t>();
+    r.stream = hs;
+    int st = cc_label(r);
+    if (st != PRL_OK) return st;
+    int found = 0;
+    for (int i = 0; i < n; ++i) {
+        found += r.pinned[i];
+        if (n_found) n_found[i] = r.pinned[i];
+        if (n_kept) n_kept[i] = 0;
+    }
+    int32_t* h_off = r.pinned + cc_pinned_bytes(n) / sizeof(int32_t);   // n + 1 values behind the labeller's
+    std::vector<int32_t> seen((size_t)n, 0);
+    j.rects = cc_pass_rects(r);
+    int32_t* d_off = w.small<int32_t>();
+    j.offsets = d_off;
+    j.thr = reinterpret_cast<int32_t*>(w.small() + off_bytes);
+    j.rect_base = 0;
+    const int pass = cc_pass_components();
+    for (int c0 = 0; c0 < found; c0 += pass) {
+        if ((st = cc_stats_pass(r, c0, std::min(pass, found - c0), nullptr)) != PRL_OK) return st;
+        if ((st = cc_read_kept(r)) != PRL_OK) return st;
+        h_off[0] = 0;
+        for (int i = 0; i < n; ++i) {   // the pass's rectangles lie page after page
+            h_off[i + 1] = h_off[i] + (r.pinned[n + i] - seen[(size_t)i]);
+            seen[(size_t)i] = r.pinned[n + i];
+            if (n_kept) n_kept[i] = seen[(size_t)i];
+        }
+        const int total = h_off[n];
+        PRL_HIP_CHECK(hipMemcpyAsync(d_off, h_off, ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, hs));
+        for (int r0 = 0; r0 < total; r0 += kRectChunk) {
+            j.thr_base = r0;
+            if ((st = rect_pass(j, r0, std::min(total, r0 + kRectChunk), pass_work, gray, dst, hs)) != PRL_OK) return st;
+        }
+        PRL_HIP_CHECK(hipStreamSynchronize(hs));   // (the next pass rewrites the pinned offsets and the pass's rectangles)
+    }
+    if (found == 0) PRL_HIP_CHECK(hipStreamSynchronize(hs));   // (the labeller's last upload reads the pinned block)
+    return PRL_OK;
+}
+
 int lo_batch(const PageArgs& a, int C, const LoSpec& sp, int32_t* n_found, int32_t* n_kept, void* stream)
 {
     if (a.n_pages == 0) return PRL_OK;
     const int W = a.width, H = a.height;
     const size_t plane = r256((size_t)W * H);
     const bool clahe = sp.clip_limit > 0;
-    // a page's share of the workspace beside CannyEdgeDetection's: the gray page, the edge map, the dilated map, the dilation's plane
-    const size_t per_page = 4 * plane + (clahe ? enhance_contrast_work_per_page() : 0);
+    const bool host_rects = env_knobs().lo_host_rects;
+    // a page's share of the workspace beside CannyEdgeDetection's: the gray page, the edge map, the dilated map, the dilation's
+    // plane, and the labeller's (the label plane and its block counts)
+    const size_t per_page = 4 * plane + (clahe ? enhance_contrast_work_per_page() : 0) + (host_rects ? 0 : cc_work_per_page(W, H));
     int chunk = ced_pages_per_chunk(sp.ced, a.n_pages, W, H, 1, per_page);
-    chunk = std::min(chunk, (int)std::max<size_t>(1, ((size_t)1 << 30) / plane));   // the read-back's pinned block: 1 GiB at most
+    if (host_rects) chunk = std::min(chunk, (int)std::max<size_t>(1, ((size_t)1 << 30) / plane));   // the read-back's pinned block: 1 GiB at most
     const size_t contrast_bytes = clahe ? r256(enhance_contrast_work_bytes(chunk)) : 0;
     const size_t ced_bytes = r256(ced_work_bytes(sp.ced, chunk, W, H, 1));
-    // [gray | edges | dilated | dilation's plane | contrast | CannyEdgeDetection, later the rectangles and their pass]
-    const size_t rect_bytes = r256((size_t)kRectChunk * 16) + rect_pass_bytes(kRectChunk);
+    // [gray | edges | dilated | dilation's plane | contrast | CannyEdgeDetection, later a pass of rect_pass (on the host path behind
+    // its rectangles) | the labeller]
+    const size_t rect_bytes = (host_rects ? r256((size_t)kRectChunk * 16) : 0) + rect_pass_bytes(kRectChunk);
     const size_t off_bytes = r256(((size_t)chunk + 1) * sizeof(int32_t));
+    const size_t stage_bytes = std::max(ced_bytes, rect_bytes);
     WorkScope w;
-    int st = w.open(stream, 4 * plane * (size_t)chunk + contrast_bytes + std::max(ced_bytes, rect_bytes),
-                    std::max(ced_small_bytes(chunk, 1), off_bytes + r256((size_t)kRectChunk * sizeof(int32_t))),
-                    std::max(ced_pinned_bytes(chunk, 1), plane * (size_t)chunk));
+    int st = w.open(stream, 4 * plane * (size_t)chunk + contrast_bytes + stage_bytes + (host_rects ? 0 : cc_work_bytes(chunk, W, H)),
+                    std::max(ced_small_bytes(chunk, 1), off_bytes + r256((size_t)kRectChunk * sizeof(int32_t)) + (host_rects ? 0 : cc_small_bytes(chunk))),
+                    std::max(ced_pinned_bytes(chunk, 1), host_rects ? plane * (size_t)chunk : cc_pinned_bytes(chunk) + off_bytes));
     if (st != PRL_OK) return st;
     const hipStream_t hs = w.stream;
     uint8_t* G = w.scratch();
@@ -276,9 +374,8 @@ int lo_batch(const PageArgs& a, int C, const LoSpec& sp, int32_t* n_found, int32
     uint8_t* T = D + plane * (size_t)chunk;
     uint8_t* contrast_work = T + plane * (size_t)chunk;
     uint8_t* stage_work = contrast_work + contrast_bytes;
+    uint8_t* cc_work = stage_work + stage_bytes;
     const int imax = imax_of(sp.max_value);
-    std::vector<std::vector<CtRect>> rects;
-    std::vector<int32_t> offsets, flat;
     for (int first = 0; first < a.n_pages; first += chunk) {
         const int n = std::min(chunk, a.n_pages - first);
         const PageSet src = src_pages(a, first);
@@ -297,43 +394,15 @@ int lo_batch(const PageArgs& a, int C, const LoSpec& sp, int32_t* n_found, int32
         const PageSetOut ep = page_set_out(E, plane, (size_t)W), dp = page_set_out(D, plane, (size_t)W);
         if ((st = ced_run(sp.ced, gray, ep, n, W, H, 1, stage_work, w.small(), w.pinned<unsigned>(), hs)) != PRL_OK) return st;
         if ((st = gmorph_dilate_rect_run(7, W, H, as_source(ep), dp, n, T, hs)) != PRL_OK) return st;
-        // 5. the one read-back; 6. the rectangles, a page per task
-        uint8_t* h_maps = w.pinned();
-        PRL_HIP_CHECK(hipMemcpyAsync(h_maps, D, plane * (size_t)n, hipMemcpyDeviceToHost, hs));
         if ((st = fill255(dst, n, W, H, hs)) != PRL_OK) return st;
-        PRL_HIP_CHECK(hipStreamSynchronize(hs));
-        rects.assign((size_t)n, std::vector<CtRect>());
-        host_pool_for(n, [&](int i) {
-            const int found = ct_external_rects(h_maps + plane * (size_t)i, (size_t)W, W, H, &rects[(size_t)i]);
-            if (n_found) n_found[first + i] = found;
-            if (n_kept) n_kept[first + i] = (int32_t)rects[(size_t)i].size();
-        });
-        // 7. their upload, the thresholds and the paint, kRectChunk rectangles a pass
-        offsets.assign((size_t)n + 1, 0);
-        flat.clear();
-        for (int i = 0; i < n; ++i) {
-            for (const CtRect& r : rects[(size_t)i]) flat.insert(flat.end(), {r.x, r.y, r.w, r.h});
-            if (flat.size() / 4 > 0x7fffffffu) return bad_arg("binarizeLocalOtsu: too many rectangles");
-            offsets[(size_t)i + 1] = (int32_t)(flat.size() / 4);
-        }
-        const int total = offsets[(size_t)n];
-        int32_t* d_off = w.small<int32_t>();
-        int32_t* d_thr = reinterpret_cast<int32_t*>(w.small() + off_bytes);
-        int32_t* d_rects = reinterpret_cast<int32_t*>(stage_work);
-        uint8_t* pass_work = stage_work + r256((size_t)kRectChunk * 16);
-        PRL_HIP_CHECK(hipMemcpyAsync(d_off, offsets.data(), ((size_t)n + 1) * sizeof(int32_t), hipMemcpyHostToDevice, hs));
+        // 5. the labels; 6. the rectangles; 7. the thresholds and the paint, kRectChunk rectangles a pass
         RectJob j{};
         j.W = W; j.H = H; j.n_pages = n; j.all_black = imax != 255;
-        j.rects = d_rects; j.offsets = d_off;
-        for (int r0 = 0; r0 < total; r0 += kRectChunk) {
-            const int r1 = std::min(total, r0 + kRectChunk);
-            PRL_HIP_CHECK(hipMemcpyAsync(d_rects, flat.data() + 4 * (size_t)r0, (size_t)(r1 - r0) * 16, hipMemcpyHostToDevice, hs));
-            j.rect_base = r0;
-            j.thr = d_thr;
-            j.thr_base = r0;
-            if ((st = rect_pass(j, r0, r1, pass_work, gray, dst, hs)) != PRL_OK) return st;
-        }
-        PRL_HIP_CHECK(hipStreamSynchronize(hs));   // `flat` and `offsets` are reused by the next chunk
+        int32_t* found = n_found ? n_found + first : nullptr;
+        int32_t* kept = n_kept ? n_kept + first : nullptr;
+        st = host_rects ? lo_rects_host(w, D, plane, n, W, H, j, stage_work, off_bytes, gray, dst, found, kept)
+                        : lo_rects_device(w, as_source(dp), n, W, H, j, cc_work, stage_work, gray, dst, found, kept);
+        if (st != PRL_OK) return st;
     }
     return PRL_OK;
 }

@@ -113,6 +113,8 @@ const EnvKnobs& env_knobs()
         k.lines_bytes = geti("PRL_HIP_LINES_BYTES", 0) != 0;
         k.stage_chunk_pages = (int)std::max(0ll, std::min(65535ll, geti("PRL_HIP_STAGE_CHUNK", 0)));
         k.bgnorm_lds_map = (int)std::max(0ll, std::min(60000ll, geti("PRL_HIP_BGNORM_LDS_MAP", 60000)));
+        k.lo_host_rects = geti("PRL_HIP_LO_HOST_RECTS", 1) != 0;
+        k.cc_pass = (int)std::max(1ll, std::min(1ll << 20, geti("PRL_HIP_CC_PASS", 1 << 20)));
         k.segmax_cap = (unsigned)std::max(64ll, std::min(1ll << 20, geti("PRL_HIP_SEGMAX_CAP", 1 << 20)));
         k.force_exact = geti("PRL_HIP_FORCE_EXACT", 0) != 0;
 #endif

@@ -134,6 +134,8 @@ struct EnvKnobs {
     bool lines_bytes = false;     // PRL_HIP_LINES_BYTES=1     removeLines' openings on byte masks through k_gm_span (lines.hip)
     int stage_chunk_pages = 0;    // PRL_HIP_STAGE_CHUNK=n     (tests) the stage entries take at most n pages per chunk (stage_chunk below; 0: off)
     int bgnorm_lds_map = 60000;   // PRL_HIP_BGNORM_LDS_MAP=n  (tests) the largest map in bytes k_bg_maps copies into LDS (bgnorm.hip; 0: every map stays in global memory)
+    bool lo_host_rects = true;    // PRL_HIP_LO_HOST_RECTS=0   binarizeLocalOtsu takes its rectangles from components.hip instead of reading its edge maps back for the host scan (contour.h): the A/B of the two paths (the device path measured no faster: profiles/r24/INDEX.md)
+    int cc_pass = 1 << 20;        // PRL_HIP_CC_PASS=n         (tests) components per statistics pass of components.hip
 };
 const EnvKnobs& env_knobs();
 
@@ -580,6 +582,37 @@ size_t enhance_contrast_work_bytes(int chunk);
 size_t enhance_contrast_work_per_page();
 int enhance_contrast_gray_run(double clip_limit, const PageSet& src, const PageSetOut& dst, int n, int W, int H, int chunk, uint8_t* work,
                               hipStream_t stream);
+
+// ---- connected components and rule R's rectangles (components.hip; the rules: include/prl_hip.h) of n maps (a chunk) of W x H on a
+// caller's workspace.  work: cc_work_bytes(n, W, H), 256-byte aligned - the label planes, the scan's block counts, one pass of
+// statistics and rectangles; small: cc_small_bytes(n); pinned: cc_pinned_bytes(n).  The caller holds ctx->mu. ----------
+struct CcRun {
+    PageSet maps;
+    int n = 0, W = 0, H = 0;
+    int connectivity = 8;     // the foreground's: 8 or 4 (the background is always 4-connected)
+    bool external = true;     // number rule R's external components only, not every foreground component
+    uint8_t* work = nullptr;
+    uint8_t* small = nullptr;
+    int32_t* pinned = nullptr;
+    hipStream_t stream = nullptr;
+};
+size_t cc_work_per_page(int W, int H);   // the part of the workspace that grows with the pages
+size_t cc_work_bytes(int n, int W, int H);
+size_t cc_small_bytes(int n);
+size_t cc_pinned_bytes(int n);
+int cc_pass_components();                // components a statistics pass takes at most
+// Labels, outer flags and the numbering.  Waits for the stream; then r.pinned[i] = the components numbered on page i (n_found), and
+// the device holds their prefix sums: component k of page i is number r.pinned[0] + .. + r.pinned[i - 1] + k of the chunk.
+int cc_label(const CcRun& r);
+// The statistics of components [c0, c0 + m) of the chunk, m <= cc_pass_components(); then either their five numbers to
+// d_stats[5 (c - c0)] (device), or the kept filter and the ordered compaction: the pass's kept rectangles to cc_pass_rects(r), x, y,
+// w, h each.  Enqueues only.  cc_read_kept waits for the stream; then r.pinned[n + i] = the rectangles page i has kept in the
+// passes since cc_label (they lie page after page in a pass: a pass's per-page share is the difference to the previous read).
+int cc_stats_pass(const CcRun& r, int c0, int m, int32_t* d_stats);
+int32_t* cc_pass_rects(const CcRun& r);
+int cc_read_kept(const CcRun& r);
+// 0 / 1 .. K into a caller's label planes (rows step bytes apart); enqueues only
+int cc_write_labels(const CcRun& r, int32_t* d_labels, size_t page_stride, size_t step);
 
 // ---- cv::HoughLines(rho 1, theta pi / 180) (hough.hip): the sizes of a W x H map's transform, per page and rounded to 256 bytes ----
 struct HoughPlan {
