@@ -1001,6 +1001,154 @@ int prl_hip_binarize_local_otsu_host(int channels, double max_value, double clah
                                      double lower_coeff, int morph_iterations, const uint8_t* src, size_t src_step, int width, int height,
                                      uint8_t* dst, size_t dst_step, int32_t* n_found, int32_t* n_kept);
 
+/* ---- cv::bilateralFilter on 8-bit planes (bilateral.hip, bilateral.h) ----------------------------------------- */
+
+#define PRL_BILATERAL_MAX_SIDE 31    /* the largest side 2 * radius + 1; above it PRL_ERR_BAD_ARG with a detail string */
+#define PRL_BILATERAL_MAX_TAPS 708   /* the taps of that side: the lattice points of a disc of radius 15, without its centre */
+
+/*
+ * cv::bilateralFilter(src, dst, d, sigmaColor, sigmaSpace) on 8-bit pages of 1 to 4 interleaved channels, EVERY CHANNEL FILTERED AS A
+ * PLANE OF ITS OWN (the one-channel path of bilateralFilter_8u; the only form the reference calls: binarizeFBCITB splits its
+ * channels, binarizeNativeAdaptive filters a mask), BORDER_REFLECT_101.  The rule is ONE form, that of the OpenCV 4.x scalar /
+ * baseline path whose tap list leaves the centre pixel out [upstream: bilateral_filter.dispatch.cpp / .simd.hpp, stated from memory,
+ * the release that introduced it not pinned; parity unpinned, DESIGN.md §2]:
+ *   sigmas     a sigma <= 0 becomes 1.
+ *   radius     d <= 0: cvRound(sigmaSpace * 1.5) (ties to even), else d / 2; then max(radius, 1).  The side is 2 * radius + 1, here
+ *              at most PRL_BILATERAL_MAX_SIDE.
+ *   tables     float64 gc = -0.5 / sigmaColor^2, gs = -0.5 / sigmaSpace^2; color[i] = (float)std::exp(i * i * gc), i = 0 .. 255;
+ *              taps (i, j) in row-major order, i (rows) outer, both from -radius to radius: r = std::sqrt((double)i * i + (double)j * j);
+ *              a tap with r > radius is skipped, and so is the centre; space[k] = (float)std::exp(r * r * gs).  12 taps at d = 5.
+ *   per pixel  c its byte, v a tap's byte; all in float32, every operation rounded on its own (no fused multiply-add), denormal
+ *              weights kept (color[14] at sigmaColor 1 is one): sum = wsum = 0; for every tap in order w = space[k] * color[|v - c|],
+ *              sum += v * w, wsum += w; dst = (uchar)cvRound((sum + c) / (wsum + 1.f)), an IEEE division, ties to even.
+ * NOT restated: the centre-first form of older lines (the centre a tap of its own, sum / wsum), which gives other bytes; the
+ * joint colour distance of 3-channel images; float32 input; other borders; accelerator builds (IPP).
+ * Pages smaller than the radius are filtered through their reflections.  One kernel; needs no workspace; its only global write
+ * is the destination.
+ * Checked in this order, before any device is touched: PRL_ERR_EMPTY (width or height <= 0); PRL_ERR_BAD_ARG (channels outside 1..4; a
+ * NaN or infinite sigma; a side above PRL_BILATERAL_MAX_SIDE, with a detail string; a null page pointer; negative n_pages; a step
+ * below the row bytes; width or height above 32768; source and destination sharing a byte: src == dst is refused).  n_pages == 0 is
+ * PRL_OK.
+ */
+
+/* The rules on the host, no device needed: *radius, *n_taps, and where the pointer is not NULL the taps' offsets dy / dx and
+ * space weights in tap order (room for PRL_BILATERAL_MAX_TAPS each) and the 256 colour weights.  PRL_ERR_BAD_ARG for a null radius
+ * or n_taps, a NaN or infinite sigma, or a side above the limit (*radius is still written, *n_taps = 0). */
+int prl_hip_bilateral_tables(int d, double sigma_color, double sigma_space, int* radius, int* n_taps, int8_t* dy, int8_t* dx,
+                             float* space_weight, float* color_weight);
+/* n pages per call; pages and rows may be strided.  Enqueues on `stream` and does not synchronise; d_src is never written. */
+int prl_hip_bilateral_filter_batch_device(int n_pages, int channels, int d, double sigma_color, double sigma_space, const uint8_t* d_src,
+                                          size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                          size_t dst_page_stride, size_t dst_step, void* stream);
+/* One page in host memory, through the staging area.  Same checks (no page count; the two may not overlap either). */
+int prl_hip_bilateral_filter_host(int channels, int d, double sigma_color, double sigma_space, const uint8_t* src, size_t src_step,
+                                  int width, int height, uint8_t* dst, size_t dst_step);
+
+/* ---- binarizeFBCITB (src/binarizations/binarizeFBCITB.cpp:73-404): fbcitb.hip, fbcitb.h, contour.h; DESIGN.md §4.4q ------------- */
+
+/*
+ * The variance mask (binarizeFBCITB.cpp:172-183): MatToLocalVarianceMap(page, map, 3) > threshold on every channel, the channels
+ * AND-ed to a 0 / 255 byte plane (convertScaleAbs(., 255, 0) changes nothing on it).  Pages of 1 or 3 channels; a gray page stands
+ * for three equal channels.  The map is max((float)D * (1.f / (9.f * 9.f)), 0.01f) with D = 9 * sum(p^2) - sum(p)^2 over the 3 x 3
+ * window of the edge-replicated page, an integer below 2^24 (binarizeByLocalVariances above).  The comparison is made in float32
+ * against (float)threshold [upstream: cv::compare converts the scalar to the array's depth; parity unpinned].  The map is monotone
+ * in D, so the host finds once per call the smallest D that passes and the kernel compares integers: a threshold below the 0.01
+ * floor passes every pixel, a NaN or one above the largest map value none.
+ * PRL_ERR_EMPTY; PRL_ERR_BAD_CHANNELS (not 1 or 3); PRL_ERR_BAD_ARG (the pages, as for the filters above).  Enqueues on `stream`.
+ */
+int prl_hip_variance_mask_batch_device(int n_pages, int channels, double threshold, const uint8_t* d_src, size_t src_page_stride,
+                                       size_t src_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride, size_t dst_step,
+                                       void* stream);
+
+/*
+ * cv::findContours(map, RETR_TREE, CHAIN_APPROX_SIMPLE) on an 8UC1 map in host memory, in OpenCV's output order [upstream, from
+ * memory; parity unpinned].  points: x, y per point, the borders one after the other (followed as "document contour" states);
+ * contours: six int32 per border - its number of points, 1 for a hole border, and the hierarchy's next, previous, first child and
+ * parent (-1: none).  Parents are the topological ones: an outer border's parent is the hole border of the background region
+ * (4-connected) round its component (8-connected), none in the outer background; a hole border's parent is its component's outer
+ * border.  A new border enters at the HEAD of its parent's child list and the output is the pre-order walk, so siblings come last
+ * discovered first (the RETR_CCOMP order of prl_hip_find_contours, nested).  n_points / n_contours always receive the totals; the
+ * arrays are written only if both have room.  Host code, no device.  PRL_ERR_EMPTY, then PRL_ERR_BAD_ARG (null, step < width, a
+ * side above 32768).
+ */
+int prl_hip_find_contours_tree(const uint8_t* map, size_t step, int width, int height, int32_t* points, int max_points, int32_t* contours,
+                               int max_contours, int* n_points, int* n_contours);
+/*
+ * RemoveChildrenContours (imageLibCommon.cpp:483-523, 641-780) on a hierarchy in the layout above, in pre-order: approved[i] = 1 for
+ * the contours it keeps.  Literally: the walk starts at contour 0 and follows `next`; a contour of fewer than 3 points is ignored;
+ * one with fewer than 6 descendants is approved and its direct children are ignored (deeper ones are never visited, hence not
+ * kept); otherwise it is ignored and the walk descends into its children.  Host code.  PRL_ERR_BAD_ARG for a null pointer, a link
+ * outside the list or a list that is not in pre-order.
+ */
+int prl_hip_remove_children_contours(const int32_t* contours, int n_contours, uint8_t* approved);
+/*
+ * binarizeFBCITB.cpp:196-357 on one page in host memory: `map` the contour map, `gray` the processed page after COLOR_BGR2GRAY
+ * (after GRAY2BGR its three channels are equal, so the AND of the reference's three channel masks is the gray decision).
+ *   contours   prl_hip_find_contours_tree, then prl_hip_remove_children_contours
+ *   filters    on cv::boundingRect: area > 10, area < int(max_area * width * height), rect width < int(0.8 * width), rect height <
+ *              int(0.8 * height)
+ *   F          the float32 sum of the gray bytes at the contour's points in point order, then (float)((double)F * (1. / N))
+ *   B          element size / 2 of the sorted gray bytes at those of the twelve corner neighbours (:284-331) that lie on the page;
+ *              never empty for a kept contour (the width filter leaves two columns outside the rectangle: fbcitb.h)
+ *   decision   F < B: a pixel p becomes 255 iff p >= F, else iff p < F.  cv::compare of bytes with a scalar is the exact real
+ *              comparison [upstream], so with cut = ceil(F) these are p >= cut and p < cut.
+ * rects: six int32 per kept contour in index order - x, y, width, height, cut, below (1: white iff p < cut) - written only if
+ * max_rects has room; counts: contours found, approved by RemoveChildrenContours, kept by the filters.  Host code.
+ */
+int prl_hip_fbcitb_contours(const uint8_t* map, size_t map_step, const uint8_t* gray, size_t gray_step, int width, int height,
+                            double max_area, int32_t* rects, int max_rects, int32_t counts[3]);
+/*
+ * The ordered paint (:359-390): d_dst = 255, then for every rectangle IN INDEX ORDER its pixels become 255 or 0 by its decision on
+ * the gray page; where rectangles overlap the one with the larger index wins.  rect_offsets (HOST, n_pages + 1 values, the first 0,
+ * not decreasing); d_rects (DEVICE, six int32 each as above); a rectangle that does not lie on the page is ignored.  Not
+ * serialised: an int32 owner plane per page, atomicMax of index + 1 over every rectangle (a wavefront per rectangle of at most
+ * 4096 pixels, larger ones sliced over 32 workgroups), and a resolve pass.  Enqueues on `stream`.
+ * PRL_ERR_EMPTY; PRL_ERR_BAD_ARG (the pages; gray and destination sharing a byte; null or malformed offsets; d_rects null with
+ * rectangles to read).
+ */
+int prl_hip_rect_paint_batch_device(int n_pages, const int32_t* rect_offsets, const int32_t* d_rects, const uint8_t* d_gray,
+                                    size_t gray_page_stride, size_t gray_step, int width, int height, uint8_t* d_dst, size_t dst_page_stride,
+                                    size_t dst_step, void* stream);
+
+/* prl::binarizeFBCITB's arguments behind the two images, with the reference's defaults (binarizeFBCITB.h:87-103) */
+typedef struct prl_fbcitb_params {
+    int32_t use_canny, use_variances_map, use_clahe, use_bilateral;
+    int32_t use_other_colorspace;          /* unused, as in the reference */
+    int32_t use_morphology, use_canny_on_variances;
+    int32_t bilateral_kernel_size;
+    double variance_map_threshold, clahe_clip_limit, gaussian_blur_kernel_size;
+    double canny_upper_threshold_coeff, canny_lower_threshold_coeff;
+    double bounding_rectangle_max_area;
+    double bilateral_kernel_intensity_sigma, bilateral_kernel_spatial_sigma;
+    double bounding_rect_max_area_coeff;   /* unused, as in the reference */
+} prl_fbcitb_params;
+void prl_hip_default_fbcitb_params(prl_fbcitb_params* p);
+
+/*
+ * prl::binarizeFBCITB on pages of 1 or 3 channels (BGR) -> width x height masks.  A gray page stands for the three equal channels
+ * the reference makes of it (every stage works per channel, and COLOR_BGR2GRAY of equal channels is the channel).
+ *   flags      use_canny and use_variances_map both 0 switches both stages on while the flags "required" stay 0: the contours then
+ *              come from the variance mask alone, without the AND (and CannyEdgeDetection's map, which the reference computes and
+ *              drops, is not computed; its argument checks still hold).
+ *   1. use_clahe: EnhanceLocalContrastByCLAHE(clip, equalize = false) per channel; use_bilateral: the bilateral filter above per
+ *      channel (bilateral_kernel_size, intensity sigma, spatial sigma)
+ *   2. use_canny: CannyEdgeDetection(processed page, int(gaussian_blur_kernel_size), upper, lower, 1)
+ *   3. use_variances_map: the variance mask of the ORIGINAL page; use_canny_on_variances: cv::Canny(64, 128) on it; both flags
+ *      required: mask &= Canny's map.  The contour map is the mask, or Canny's map when only use_canny is set.
+ *   4. the gray plane of the processed page (COLOR_BGR2GRAY); ONE read-back of map and gray plane per chunk of pages
+ *   5. prl_hip_fbcitb_contours per page on the host thread pool; the rectangles go up; prl_hip_rect_paint_batch_device's kernels
+ *   6. use_morphology: cv::dilate 3 x 3 twice, then cv::erode twice
+ * A page without contours is all 255.  counts (HOST, three int32 per page, or NULL): contours found / approved / kept.
+ * Checked in this order: PRL_ERR_EMPTY; PRL_ERR_BAD_CHANNELS (not 1 or 3); PRL_ERR_BAD_ARG (null params; a parameter that is not
+ * finite; a bilateral side above PRL_BILATERAL_MAX_SIDE; with the Canny stage on, CannyEdgeDetection's argument checks);
+ * PRL_ERR_BAD_WINDOW (a blur side above PRL_GAUSS_MAX_SIDE); PRL_ERR_BAD_ARG (the pages).  Waits for the stream.
+ */
+int prl_hip_binarize_fbcitb_batch_device(const prl_fbcitb_params* params, int n_pages, int channels, const uint8_t* d_src,
+                                         size_t src_page_stride, size_t src_step, int width, int height, uint8_t* d_dst,
+                                         size_t dst_page_stride, size_t dst_step, int32_t* counts, void* stream);
+int prl_hip_binarize_fbcitb_host(const prl_fbcitb_params* params, int channels, const uint8_t* src, size_t src_step, int width, int height,
+                                 uint8_t* dst, size_t dst_step, int32_t* counts);
+
 /* ---- adaptive-threshold binarizers (prl::binarizeNativeAdaptive, binarizeAT, binarizeAGT, binarizePureAdaptiveGaussian) ---- */
 
 #define PRL_ADAPTIVE_MEAN_C 0      /* cv::ADAPTIVE_THRESH_MEAN_C */

@@ -15,6 +15,8 @@ from .detectors import focusFromSums, focusMeasures, focusSums  # noqa: F401
 from .deblur import basicDeblur, gaussianBlurF32, gaussianBlurSize, gaussianKernelF32  # noqa: F401
 from .contrast import clahe, claheGeometry, claheLuts, claheTileLut, enhanceLocalContrast, equalizeHist, equalizeHistLut  # noqa: F401
 from .components import connectedComponents  # noqa: F401
+from .fbcitb import (bilateralFilter, bilateralTables, binarizeFBCITB, fbcitbContours, findContoursTree, rectPaint,  # noqa: F401
+                     removeChildrenContours, varianceMask)
 from .localotsu import (binarizeLocalOtsu, cannyEdgeDetection, externalRects, gaussianBlurU8, gaussianKernelU8, rectOtsu,  # noqa: F401
                         sepFilterU8)
 from .thinning import thinGuoHall, thinZhangSuen  # noqa: F401

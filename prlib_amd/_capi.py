@@ -88,6 +88,10 @@ EXPORTED_SYMBOLS = [
     "prl_hip_gaussian_blur_u8_host", "prl_hip_canny_edge_detection_batch_device", "prl_hip_canny_edge_detection_host",
     "prl_hip_external_rects", "prl_hip_rect_otsu_batch_device", "prl_hip_binarize_local_otsu_batch_device",
     "prl_hip_binarize_local_otsu_host", "prl_hip_connected_components_batch_device", "prl_hip_external_rects_batch_device",
+    "prl_hip_bilateral_tables", "prl_hip_bilateral_filter_batch_device", "prl_hip_bilateral_filter_host",
+    "prl_hip_variance_mask_batch_device", "prl_hip_find_contours_tree", "prl_hip_remove_children_contours", "prl_hip_fbcitb_contours",
+    "prl_hip_rect_paint_batch_device", "prl_hip_default_fbcitb_params", "prl_hip_binarize_fbcitb_batch_device",
+    "prl_hip_binarize_fbcitb_host",
 ]
 
 
@@ -119,6 +123,17 @@ class AdaptiveParams(C.Structure):
 
     _fields_ = [("median_ksize", C.c_int32), ("median_on_color", C.c_int32), ("method", C.c_int32), ("type", C.c_int32),
                 ("max_value", C.c_double), ("block_size", C.c_int32), ("auto_invert", C.c_int32), ("delta", C.c_double)]
+
+
+class FbcitbParams(C.Structure):
+    """struct prl_fbcitb_params."""
+
+    _fields_ = [(n, C.c_int32) for n in ("use_canny", "use_variances_map", "use_clahe", "use_bilateral", "use_other_colorspace",
+                                          "use_morphology", "use_canny_on_variances", "bilateral_kernel_size")] + \
+               [(n, C.c_double) for n in ("variance_map_threshold", "clahe_clip_limit", "gaussian_blur_kernel_size",
+                                          "canny_upper_threshold_coeff", "canny_lower_threshold_coeff", "bounding_rectangle_max_area",
+                                          "bilateral_kernel_intensity_sigma", "bilateral_kernel_spatial_sigma",
+                                          "bounding_rect_max_area_coeff")]
 
 
 class BinarizeGeometry(C.Structure):
@@ -315,6 +330,18 @@ def lib() -> C.CDLL:
         L.prl_hip_binarize_local_otsu_host.argtypes = [i, d, d, i, d, d, i, vp, sz, i, i, vp, sz, vp, vp]
         L.prl_hip_connected_components_batch_device.argtypes = [i, i, vp, sz, sz, i, i, vp, sz, sz, vp, vp, i, vp]
         L.prl_hip_external_rects_batch_device.argtypes = [i, vp, sz, sz, i, i, vp, i, vp, vp, vp, vp]
+        L.prl_hip_bilateral_tables.argtypes = [i, d, d, P(C.c_int), P(C.c_int), vp, vp, vp, vp]
+        L.prl_hip_bilateral_filter_batch_device.argtypes = [i, i, i, d, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_bilateral_filter_host.argtypes = [i, i, d, d, vp, sz, i, i, vp, sz]
+        L.prl_hip_variance_mask_batch_device.argtypes = [i, i, d, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_find_contours_tree.argtypes = [vp, sz, i, i, vp, i, vp, i, P(C.c_int), P(C.c_int)]
+        L.prl_hip_remove_children_contours.argtypes = [vp, i, vp]
+        L.prl_hip_fbcitb_contours.argtypes = [vp, sz, vp, sz, i, i, d, vp, i, vp]
+        L.prl_hip_rect_paint_batch_device.argtypes = [i, vp, vp, vp, sz, sz, i, i, vp, sz, sz, vp]
+        L.prl_hip_default_fbcitb_params.argtypes = [P(FbcitbParams)]
+        L.prl_hip_default_fbcitb_params.restype = None
+        L.prl_hip_binarize_fbcitb_batch_device.argtypes = [P(FbcitbParams), i, i, vp, sz, sz, i, i, vp, sz, sz, vp, vp]
+        L.prl_hip_binarize_fbcitb_host.argtypes = [P(FbcitbParams), i, vp, sz, i, i, vp, sz, vp]
         _lib = L
     return _lib
 

@@ -455,6 +455,16 @@ int enhance_contrast_gray_run(double clip_limit, const PageSet& s, const PageSet
     return contrast_chunk(1, sp, s, d, n, W, H, contrast_work(1, sp, false), chunk, work, nullptr, hs);
 }
 
+// the same with C interleaved channels and either flag (prl::binarizeFBCITB, fbcitb.hip: three channels, no equalization), in place or not
+size_t enhance_contrast_channels_work_bytes(int C, bool equalize, int chunk) { return contrast_work(C, clahe_spec(40.0, 8, 8, equalize), false).bytes(chunk); }
+size_t enhance_contrast_channels_work_per_page(int C, bool equalize) { return contrast_work(C, clahe_spec(40.0, 8, 8, equalize), false).per_page(); }
+int enhance_contrast_channels_run(int C, bool equalize, double clip_limit, const PageSet& s, const PageSetOut& d, int n, int W, int H, int chunk,
+                                  uint8_t* work, hipStream_t hs)
+{
+    const ContrastSpec sp = clahe_spec(clip_limit, 8, 8, equalize);
+    return contrast_chunk(C, sp, s, d, n, W, H, contrast_work(C, sp, false), chunk, work, nullptr, hs);
+}
+
 }  // namespace prl_hip
 
 using namespace prl_hip;

@@ -204,6 +204,167 @@ inline int ct_external_rects(const uint8_t* map, size_t step, int w, int h, std:
     return found;
 }
 
+// points [first, first + count) of the list that comes with it, and cv::findContours' four hierarchy links (-1: none)
+struct CtNode {
+    int first, count, hole;
+    int next, prev, child, parent;
+};
+
+// cv::findContours(map, RETR_TREE, CHAIN_APPROX_SIMPLE): every border with its hierarchy, in OpenCV's output order [upstream, from
+// memory].  The scan and the border following are ct_find_contours'.  The parents are the topological ones: an outer border's
+// parent is the hole border of the background region round its component (none for the outer background), a hole border's parent
+// is the outer border of the component it lies in - what OpenCV's border numbers give, and what it falls back to by tracing when
+// its 7-bit numbers collide.  A hole region (background, 4-connected) is labelled when its border starts: its first pixel in
+// raster order comes before every component inside it.  A new border goes to the HEAD of its parent's child list, and the output
+// is the pre-order walk: siblings appear last discovered first, as in ct_find_contours' RETR_CCOMP order.
+inline void ct_find_contours_tree(const uint8_t* map, size_t step, int w, int h, std::vector<CtPoint>* points, std::vector<CtNode>* nodes)
+{
+    points->clear();
+    nodes->clear();
+    const int pw = w + 2;
+    std::vector<signed char> img((size_t)pw * (h + 2), 0);   // one pixel of background all round
+    for (int y = 0; y < h; ++y)
+        for (int x = 0; x < w; ++x) img[(size_t)(y + 1) * pw + x + 1] = map[(size_t)y * step + x] != 0;
+    int deltas[16];
+    for (int d = 0; d < 16; ++d) deltas[d] = kCtDy[d & 7] * pw + kCtDx[d & 7];
+
+    struct Found {
+        int first, count, hole, parent;   // parent: an index of `found`
+    };
+    std::vector<Found> found;
+    std::vector<CtPoint> raw;
+    // per foreground pixel: its component's outer border; per background pixel of a hole: the hole's border (indices of `found`)
+    std::vector<int32_t> owner((size_t)pw * (h + 2), -1);
+    std::vector<int> queue;
+    for (int y = 1; y <= h; ++y) {
+        int prev = 0;
+        for (int x = 1; x <= w; ++x) {
+            signed char* row = img.data() + (size_t)y * pw;
+            int p = row[x];
+            if (p != prev) {
+                bool start = true, hole = false;
+                if (!(prev == 0 && p == 1)) {
+                    hole = true;
+                    if (p != 0 || prev < 1) start = false;
+                }
+                if (start) {
+                    const int x0 = x - (hole ? 1 : 0), id = (int)found.size();
+                    const int first = (int)raw.size();
+                    int parent;
+                    if (!hole) {   // the component this border encloses (8-connected); the region to its left says where it lies
+                        parent = owner[(size_t)y * pw + x0 - 1];
+                        queue.assign(1, y * pw + x0);
+                        owner[(size_t)y * pw + x0] = id;
+                        while (!queue.empty()) {
+                            const int at = queue.back();
+                            queue.pop_back();
+                            for (int d = 0; d < 8; ++d) {
+                                const int to = at + deltas[d];
+                                if (img[to] != 0 && owner[to] < 0) {
+                                    owner[to] = id;
+                                    queue.push_back(to);
+                                }
+                            }
+                        }
+                    } else {       // the hole this border encloses (4-connected): it never reaches the frame
+                        parent = owner[(size_t)y * pw + x0];
+                        queue.assign(1, y * pw + x);
+                        owner[(size_t)y * pw + x] = id;
+                        while (!queue.empty()) {
+                            const int at = queue.back();
+                            queue.pop_back();
+                            for (int d = 0; d < 8; d += 2) {
+                                const int to = at + deltas[d];
+                                if (to < 0 || to >= (int)img.size()) continue;
+                                if (img[to] == 0 && owner[to] < 0) {
+                                    owner[to] = id;
+                                    queue.push_back(to);
+                                }
+                            }
+                        }
+                    }
+                    ct_trace(row + x0, deltas, hole, CtPoint{x0 - 1, y - 1}, &raw);
+                    found.push_back({first, (int)raw.size() - first, hole ? 1 : 0, parent});
+                    p = row[x];
+                }
+            }
+            prev = p;
+        }
+    }
+    // child lists, last discovered first; then the pre-order walk
+    const int n = (int)found.size();
+    std::vector<int> head((size_t)n + 1, -1), sibling((size_t)n, -1);   // head[n]: the top level
+    for (int i = 0; i < n; ++i) {
+        const int par = found[i].parent < 0 ? n : found[i].parent;
+        sibling[i] = head[par];
+        head[par] = i;
+    }
+    std::vector<int> out_of((size_t)n, -1), order, stack;
+    for (int i = head[n]; i >= 0; i = sibling[i]) stack.push_back(i);
+    std::reverse(stack.begin(), stack.end());
+    while (!stack.empty()) {
+        const int i = stack.back();
+        stack.pop_back();
+        out_of[i] = (int)order.size();
+        order.push_back(i);
+        const size_t at = stack.size();
+        for (int c = head[i]; c >= 0; c = sibling[c]) stack.push_back(c);
+        std::reverse(stack.begin() + at, stack.end());
+    }
+    nodes->resize((size_t)n);
+    std::vector<int> last_child((size_t)n + 1, -1);   // per parent, the output index of the child emitted before
+    for (int k = 0; k < n; ++k) {
+        const Found& f = found[order[k]];
+        CtNode& nd = (*nodes)[k];
+        nd = CtNode{(int)points->size(), f.count, f.hole, -1, -1, -1, f.parent < 0 ? -1 : out_of[f.parent]};
+        points->insert(points->end(), raw.begin() + f.first, raw.begin() + f.first + f.count);
+        const int par = f.parent < 0 ? n : f.parent;
+        if (last_child[par] >= 0) {
+            nd.prev = last_child[par];
+            (*nodes)[last_child[par]].next = k;
+        } else if (f.parent >= 0) {
+            (*nodes)[out_of[f.parent]].child = k;
+        }
+        last_child[par] = k;
+    }
+}
+
+// RemoveChildrenContours with ContourChildrenCount and CheckHierarhyLevelRecursively (imageLibCommon.cpp:483-523, 641-780),
+// literally, the recursion unrolled: the walk starts at contour 0 and follows the `next` links; a contour of fewer than 3 points is
+// ignored (and its children never visited); one with no descendants is approved; with fewer than 6 descendants it is approved and
+// its direct children are ignored (their own children are never visited); otherwise it is ignored and the walk descends into its
+// children.  approved[i] = 1 for the contours the reference keeps, in index order.  Needs nodes in pre-order (a parent before its
+// children), which ct_find_contours_tree gives.
+inline void ct_remove_children(const std::vector<CtNode>& nodes, std::vector<uint8_t>* approved)
+{
+    const int n = (int)nodes.size();
+    approved->assign((size_t)n, 0);
+    if (n == 0) return;
+    std::vector<int> descendants((size_t)n, 0);
+    for (int i = n - 1; i >= 0; --i)
+        if (nodes[i].parent >= 0) descendants[nodes[i].parent] += descendants[i] + 1;
+    std::vector<signed char> state((size_t)n, 0);   // 0 not visited, 1 approved, -1 ignored
+    std::vector<int> starts(1, 0);
+    while (!starts.empty()) {
+        int cur = starts.back();
+        starts.pop_back();
+        while (cur >= 0) {
+            const CtNode& nd = nodes[cur];
+            if (nd.count < 3) {
+                state[cur] = -1;
+            } else if (descendants[cur] < 6) {
+                state[cur] = 1;
+                for (int c = nd.child; c >= 0; c = nodes[c].next) state[c] = -1;
+            } else {
+                state[cur] = -1;
+                starts.push_back(nd.child);
+            }
+            cur = nd.next;
+        }
+    }
+    for (int i = 0; i < n; ++i) (*approved)[i] = state[i] == 1;
+}
+
 // cv::approxPolyDP(src, dst, eps, closed = true) on integer points; dst has room for n points; returns the new count.
 inline int ct_approx_closed(const CtPoint* src, int n, double eps, CtPoint* dst)
 {

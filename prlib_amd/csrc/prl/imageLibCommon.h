@@ -29,5 +29,12 @@ namespace prl {
 // every channel of an 8-bit image of 1 to 4 channels.  Exceptions as above; StsBadArg also for a grid side outside 1..64.
 CV_EXPORTS void clahe(const cv::Mat& inputImage, cv::Mat& outputImage, double clipLimit = 40.0, int tilesX = 8, int tilesY = 8);
 CV_EXPORTS void equalizeHist(const cv::Mat& inputImage, cv::Mat& outputImage);
+// cv::bilateralFilter(inputImage, outputImage, d, sigmaColor, sigmaSpace) with BORDER_REFLECT_101 on an 8-bit image of 1 to 4
+// channels, EVERY CHANNEL FILTERED AS A PLANE OF ITS OWN - cv::bilateralFilter's result for one channel, and what the reference
+// computes for more by splitting them; not OpenCV's joint colour distance for 3 channels (bilateral.hip; prl_hip.h,
+// "cv::bilateralFilter").  std::invalid_argument for an empty image; cv::Exception StsUnsupportedFormat for another depth or more
+// than 4 channels, StsBadArg for a side 2 * radius + 1 above 31 or a sigma that is not finite, StsAssert when outputImage shares
+// inputImage's pixels (cv::bilateralFilter does not work in place either).
+CV_EXPORTS void bilateralFilter(const cv::Mat& inputImage, cv::Mat& outputImage, int d, double sigmaColor, double sigmaSpace);
 
 }  // namespace prl

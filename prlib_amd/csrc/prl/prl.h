@@ -23,6 +23,7 @@
 //   src/detectors/blurDetection.h:35                       prl::isBlurred (+ prl::focusMeasures)
 //   src/deblur/basicDeblur.h:32-34                         prl::basicDeblur
 //   src/binarizations/binarizeLocalOtsu.h                  prl::binarizeLocalOtsu
+//   src/binarizations/binarizeFBCITB.h                     prl::binarizeFBCITB
 //   src/warp.h:49-73                                       prl::warpCrop
 //   src/border_detection/autoCrop.h:42-53                  prl::documentContour, prl::autoCrop
 //   src/border_detection/houghLine.h                       prl::findHoughLineContour
@@ -188,6 +189,22 @@ CV_EXPORTS void basicDeblur(const cv::Mat& inputImage, cv::Mat& outputImage, con
 CV_EXPORTS void binarizeLocalOtsu(cv::Mat& inputImage, cv::Mat& outputImage, double maxValue = 255.0, double CLAHEClipLimit = 0.0,
                                   int GaussianBlurKernelSize = 19, double CannyUpperThresholdCoeff = 0.15,
                                   double CannyLowerThresholdCoeff = 0.01, int CannyMorphIters = 1);
+
+// src/binarizations/binarizeFBCITB.h - binarizeFBCITB.cpp:73-404, "font and background color independent text binarization", on an
+// 8UC3 (BGR) or one-channel 8-bit image (fbcitb.hip, bilateral.hip; the rules are stated in prl_hip.h, "binarizeFBCITB").  As in the
+// reference a one-channel inputImage is REPLACED by its cv::COLOR_GRAY2BGR conversion (the caller's Mat becomes 8UC3); a colour
+// image's pixels are never written.  useOtherColorspace and boundingRectMaxAreaCoeff are unused, as there.  An image whose contour
+// map has no contour gives an all-white mask.  std::invalid_argument with the reference's messages for an empty image and for any
+// other type ("Invalid type of image for binarization (required 24 bits per pixel)"), and CannyEdgeDetection's when that stage
+// runs; cv::Exception StsAssert for an even blur size, StsBadArg for a parameter that is not finite, a blur size above 255, a
+// bilateral side above 31 or an image side above 32768 (documented deviations).  outputImage is a new CV_8UC1 Mat.
+CV_EXPORTS void binarizeFBCITB(cv::Mat& inputImage, cv::Mat& outputImage, bool useCanny = true, bool useVariancesMap = true,
+                               bool useCLAHE = true, bool useBilateral = true, bool useOtherColorspace = false, bool useMorphology = true,
+                               bool useCannyOnVariances = true, double varianceMapThreshold = 200.0, double CLAHEClipLimit = 2.0,
+                               double gaussianBlurKernelSize = 9.0, double cannyUpperThresholdCoeff = 0.6,
+                               double cannyLowerThresholdCoeff = 0.4, double boundingRectangleMaxArea = 0.3, int bilateralKernelSize = 5,
+                               double bilateralKernelIntensitySigma = 150.0, double bilateralKernelSpatialSigma = 150.0,
+                               double boundingRectMaxAreaCoeff = 0.3);
 
 // SURVEY.md §8f rank 1 — src/thinning/thinZhangSuen.h, src/thinning/thinGuoHall.h.  8UC1 or 8UC3 (BGR is
 // converted to gray first, thinZhangSuen.cpp:78-81); foreground = pixels with bit 0 set; output 0/255.

@@ -380,6 +380,15 @@ void prl::equalizeHist(const cv::Mat& inputImage, cv::Mat& outputImage)
     });
 }
 
+void prl::bilateralFilter(const cv::Mat& inputImage, cv::Mat& outputImage, int d, double sigmaColor, double sigmaSpace)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Image for bilateral filtration is empty");
+    if (inputImage.data == outputImage.data) PRL_FAIL_CV(cv::Error::StsAssert, "src.data != dst.data");
+    contrast_call(inputImage, outputImage, "prl::bilateralFilter", [&](int cn, const unsigned char* s, size_t ss, int w, int h, unsigned char* dd, size_t ds) {
+        return prl_hip_bilateral_filter_host(cn, d, sigmaColor, sigmaSpace, s, ss, w, h, dd, ds);
+    });
+}
+
 namespace {
 
 // CannyEdgeDetection's own checks in the reference's order (imageLibCommon.cpp:253-272), then cv::GaussianBlur's assertion
@@ -431,6 +440,54 @@ void prl::binarizeLocalOtsu(cv::Mat& inputImage, cv::Mat& outputImage, double ma
                                                     inputImage.cols, inputImage.rows, result.data, result.step, &found, &kept);
     if (st != PRL_OK) raise(st);
     if (found == 0) throw std::invalid_argument("Contours array is empty");   // RemoveChildrenContours, imageLibCommon.cpp:643-646
+    outputImage = result;
+}
+
+// binarizeFBCITB.cpp:73-404 in the reference's statement order: the empty check, the type check with its side effect on a
+// one-channel image (cv::cvtColor(inputImage, inputImage, COLOR_GRAY2BGR)), then - where the Canny stage runs - CannyEdgeDetection's
+// checks.  The C layer takes the BGR page; a page without contours is all 255, as the reference's early return makes it.
+void prl::binarizeFBCITB(cv::Mat& inputImage, cv::Mat& outputImage, bool useCanny, bool useVariancesMap, bool useCLAHE, bool useBilateral,
+                         bool useOtherColorspace, bool useMorphology, bool useCannyOnVariances, double varianceMapThreshold,
+                         double CLAHEClipLimit, double gaussianBlurKernelSize, double cannyUpperThresholdCoeff,
+                         double cannyLowerThresholdCoeff, double boundingRectangleMaxArea, int bilateralKernelSize,
+                         double bilateralKernelIntensitySigma, double bilateralKernelSpatialSigma, double boundingRectMaxAreaCoeff)
+{
+    if (inputImage.empty()) throw std::invalid_argument("Input image for binarization is empty");
+    if (inputImage.type() != CV_8UC3) {
+        if (inputImage.channels() != 1 || inputImage.depth() != CV_8U)
+            throw std::invalid_argument("Invalid type of image for binarization (required 24 bits per pixel)");
+#ifdef PRL_HAVE_OPENCV
+        cv::cvtColor(inputImage, inputImage, cv::COLOR_GRAY2BGR);
+#else
+        cv::Mat bgr(inputImage.rows, inputImage.cols, CV_8UC3);
+        for (int y = 0; y < inputImage.rows; ++y) {
+            const unsigned char* s = inputImage.ptr(y);
+            unsigned char* d = bgr.ptr(y);
+            for (int x = 0; x < inputImage.cols; ++x) d[3 * x] = d[3 * x + 1] = d[3 * x + 2] = s[x];
+        }
+        inputImage = bgr;
+#endif
+    }
+    prl_fbcitb_params p;
+    prl_hip_default_fbcitb_params(&p);
+    p.use_canny = useCanny; p.use_variances_map = useVariancesMap; p.use_clahe = useCLAHE; p.use_bilateral = useBilateral;
+    p.use_other_colorspace = useOtherColorspace; p.use_morphology = useMorphology; p.use_canny_on_variances = useCannyOnVariances;
+    p.variance_map_threshold = varianceMapThreshold; p.clahe_clip_limit = CLAHEClipLimit;
+    p.gaussian_blur_kernel_size = gaussianBlurKernelSize;
+    p.canny_upper_threshold_coeff = cannyUpperThresholdCoeff; p.canny_lower_threshold_coeff = cannyLowerThresholdCoeff;
+    p.bounding_rectangle_max_area = boundingRectangleMaxArea; p.bilateral_kernel_size = bilateralKernelSize;
+    p.bilateral_kernel_intensity_sigma = bilateralKernelIntensitySigma; p.bilateral_kernel_spatial_sigma = bilateralKernelSpatialSigma;
+    p.bounding_rect_max_area_coeff = boundingRectMaxAreaCoeff;
+    if ((useCanny || !useVariancesMap) && gaussianBlurKernelSize == gaussianBlurKernelSize && gaussianBlurKernelSize < 2147483647.0 &&
+        gaussianBlurKernelSize > -2147483647.0) {
+        const int size = static_cast<int>(gaussianBlurKernelSize);
+        canny_edge_checks(size, cannyUpperThresholdCoeff, cannyLowerThresholdCoeff, __func__, __LINE__);
+        if (size > PRL_GAUSS_MAX_SIDE) PRL_FAIL_CV(cv::Error::StsBadArg, "prl::binarizeFBCITB: kernel sizes up to 255 only");
+    }
+    cv::Mat result(inputImage.rows, inputImage.cols, CV_8UC1);
+    const int st = prl_hip_binarize_fbcitb_host(&p, 3, inputImage.data, inputImage.step, inputImage.cols, inputImage.rows, result.data,
+                                                result.step, nullptr);
+    if (st != PRL_OK) raise(st);
     outputImage = result;
 }
 

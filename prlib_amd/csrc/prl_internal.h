@@ -560,6 +560,11 @@ void canny_threshold_table(double upper_coeff, double lower_coeff, int* lut);
 // pages of 1..4 channels, source and destination distinct; needs no workspace; enqueues only ----------
 int sep_filter_u8_batch(const uint16_t* wx, int nx, const uint16_t* wy, int ny, const PageArgs& a, int channels, hipStream_t stream);
 
+// ---- cv::bilateralFilter (bilateral.hip): every channel of n pages of 1..4 channels as a plane of its own, with the tables of
+// bilateral.h; source and destination distinct; needs no workspace; enqueues only ----------
+struct BilTables;
+int bilateral_planes_run(const BilTables& t, const PageArgs& a, int channels, hipStream_t stream);
+
 // ---- CannyEdgeDetection (edgedet.hip; imageLibCommon.cpp:244-324) of n pages (a chunk) of C channels into 0 / 255 maps.  work:
 // ced_work_bytes; small: ced_small_bytes; h_flags: pinned, ced_pinned_bytes.  Synchronises the stream (caller holds ctx->mu).
 // ced_pages_per_chunk: the pages a chunk takes when a page costs extra_per_page bytes beside the stage's own ------
@@ -582,6 +587,12 @@ size_t enhance_contrast_work_bytes(int chunk);
 size_t enhance_contrast_work_per_page();
 int enhance_contrast_gray_run(double clip_limit, const PageSet& src, const PageSetOut& dst, int n, int W, int H, int chunk, uint8_t* work,
                               hipStream_t stream);
+
+// the same on pages of C interleaved channels, with or without the equalization (prl::binarizeFBCITB)
+size_t enhance_contrast_channels_work_bytes(int C, bool equalize, int chunk);
+size_t enhance_contrast_channels_work_per_page(int C, bool equalize);
+int enhance_contrast_channels_run(int C, bool equalize, double clip_limit, const PageSet& src, const PageSetOut& dst, int n, int W, int H,
+                                  int chunk, uint8_t* work, hipStream_t stream);
 
 // ---- connected components and rule R's rectangles (components.hip; the rules: include/prl_hip.h) of n maps (a chunk) of W x H on a
 // caller's workspace.  work: cc_work_bytes(n, W, H), 256-byte aligned - the label planes, the scan's block counts, one pass of
